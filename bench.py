@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the EDM per-timestep bias hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input on every GPU:
   (1) bias-force evaluation for W1 = 1,048,576 pair distances of a 1-D r-CV
@@ -10,8 +10,8 @@ One "step" = one pass of the hot path over one batch of synthetic input on every
       per pair worth of estimate, bias limiting active (bias_per_step = hill_prefactor),
   in the REFERENCE FIX'S ORDER (lammps/fix_edm_pair.cpp:177-238: pair k's force is read behind the hills of the
   add_hill calls before it -- edm_hip_bias_pair_step_ordered, the default of the rewritten fix edm_pair) and with the
-  reference's per-hill HILLS log ON (the library's default).  The batched order (every force on the bias as it
-  stands after pre_add_hill: keyword batch_order) and the log-off step are timed beside it.
+  reference's per-hill HILLS log ON (the library's default).  Under --full the batched order (every force on the bias
+  as it stands after pre_add_hill: keyword batch_order) and the log-off step are timed beside it.
 Inputs are resident in HBM before the timed region.  N > 1 is weak scaling: every rank
 (one process per GPU) owns its own W1-sized pair set of the same system, hill_density is
 a per-system quantity (divided by the rank count exactly like EDMBias::subdivide does
@@ -19,7 +19,11 @@ under MPI) and ranks exchange over RCCL.  value = pairs evaluated by all ranks /
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts the N ranks itself
 (python -m torch.distributed.run, one process per GPU) before anything touches a GPU.
 
-Rank 0 prints ONE JSON line (see the driver contract) with these extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line from rank 0 (see the driver contract):
+the headline figure and nothing that needs measurements of its own.  --dump-outputs DIR writes what the last timed
+step computed (rank 0's: the pair forces and the energy, float64) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+With --full the line also carries these objects (each measured after the timed steps):
   roofline      -- the bias-force kernel of the W1 step: algorithmic 16 B/eval over its HIP-event duration
                    measured on the kernel's own stream inside the timed region; roofline.other holds the same figure
                    for W2 (38.8 M pairs, the HBM-bound capture), for K2 on the 2048^2 and 512^3 coordinate-CV grids,
@@ -258,31 +262,16 @@ def all_samples_line(args, rank, world, dist, H, W, tmpdir):
         dist.destroy_process_group()
 
 
-def headline_dict(args, world, npairs, elapsed, k_ms, k_launches, timed_every, tail_us=()):
+def headline_dict(args, world, npairs, elapsed):
     """The contract keys of the JSON line, complete once the timed region has ended."""
-    ms_per_step = elapsed / args.steps * 1e3
-    total_pairs = npairs * world
-    # the stamped launches: those of the timed region (their mean) and the stamped tail right behind it (see main());
-    # the median over all of them is the launch's duration -- one sample of a 12 us launch is what the driver's
-    # --steps 20 leaves in the timed region, and a single stamp read 20 us once where every other read 11.5
-    timed_us = k_ms / max(k_launches, 1) * 1e3
-    samples = ([timed_us] if k_launches else []) + list(tail_us)
-    samples.sort()
-    k_s = (samples[len(samples) // 2] if samples else timed_us) * 1e-6
-    # SURVEY 8(d): 16 B per evaluation (8 B distance in + 8 B force out) x the pairs one launch processes.  The
-    # reference-order launch also reads one 4-B sample index per pair (where the pair's add_hill calls begin) -- real
-    # traffic of the same launch, reported beside the 8(d) figure, not inside it
-    alg_bytes = BYTES_PER_EVAL * npairs
-    achieved = alg_bytes / k_s / 1e9
-    with_u = (alg_bytes + 4 * npairs) / k_s / 1e9
     return {
         "metric": "million bias-force evals/sec (1M-pair 1D CV, force eval + hill step per step, reference fix's order, HILLS log on)",
-        "value": total_pairs / (elapsed / args.steps) / 1e6,
+        "value": npairs * world / (elapsed / args.steps) / 1e6,
         "unit": "million evals/s",
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
+        "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -298,30 +287,64 @@ def headline_dict(args, world, npairs, elapsed, k_ms, k_launches, timed_every, t
             "hills_log": "on (edm_bias.cpp:586-599, the library's default)",
             "parallelism": "replicated bias grid, samples sharded, dp%d" % world,
         },
-        "roofline": {
-            "kernel": "k_pair_forces_ordered (K1 in the reference fix's order: each pair's two corner records as they stood behind "
-                      "the hills of the add_hill calls before it)",
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS,
-            "traffic": pmc_traffic("edm::k_pair_forces_ordered"),
-            "kernel_us": k_s * 1e6,
-            "kernel_us_timed_region": timed_us,
-            "kernel_us_samples": [round(v, 2) for v in samples],
-            "kernel_us_note": "median over the stamped launches: the timed region's (mean of `launches`) and a tail of stamped "
-                              "steps of the same loop right behind it",
-            "kernel_us_rocprof": rocprof_avg_us("edm::k_pair_forces_ordered"),
-            "launches": k_launches,
-            "timed_every": timed_every,
-            "bytes_per_launch": alg_bytes,
-            "bytes_per_launch_note": "16 B per pair (SURVEY 8d: distance in + force out)",
-            "achieved_incl_sample_indices": with_u,
-            "frac_incl_sample_indices": with_u / HBM_PEAK_GBS,
-            "bytes_per_launch_incl_sample_indices": alg_bytes + 4 * npairs,
-        },
     }
+
+
+def roofline_dict(npairs, k_ms, k_launches, timed_every, tail_us=()):
+    """(--full) the roofline object of the headline's dominant kernel, from its stamped launches."""
+    # the stamped launches: those of the timed region (their mean) and the stamped tail right behind it (see main());
+    # the median over all of them is the launch's duration -- one sample of a 12 us launch is what the driver's
+    # --steps 20 leaves in the timed region, and a single stamp read 20 us once where every other read 11.5
+    timed_us = k_ms / max(k_launches, 1) * 1e3
+    samples = ([timed_us] if k_launches else []) + list(tail_us)
+    samples.sort()
+    k_s = (samples[len(samples) // 2] if samples else timed_us) * 1e-6
+    # SURVEY 8(d): 16 B per evaluation (8 B distance in + 8 B force out) x the pairs one launch processes.  The
+    # reference-order launch also reads one 4-B sample index per pair (where the pair's add_hill calls begin) -- real
+    # traffic of the same launch, reported beside the 8(d) figure, not inside it
+    alg_bytes = BYTES_PER_EVAL * npairs
+    achieved = alg_bytes / k_s / 1e9
+    with_u = (alg_bytes + 4 * npairs) / k_s / 1e9
+    return {
+        "kernel": "k_pair_forces_ordered (K1 in the reference fix's order: each pair's two corner records as they stood behind "
+                  "the hills of the add_hill calls before it)",
+        "bound": "hbm",
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS,
+        "traffic": pmc_traffic("edm::k_pair_forces_ordered"),
+        "kernel_us": k_s * 1e6,
+        "kernel_us_timed_region": timed_us,
+        "kernel_us_samples": [round(v, 2) for v in samples],
+        "kernel_us_note": "median over the stamped launches: the timed region's (mean of `launches`) and a tail of stamped "
+                          "steps of the same loop right behind it",
+        "kernel_us_rocprof": rocprof_avg_us("edm::k_pair_forces_ordered"),
+        "launches": k_launches,
+        "timed_every": timed_every,
+        "bytes_per_launch": alg_bytes,
+        "bytes_per_launch_note": "16 B per pair (SURVEY 8d: distance in + force out)",
+        "achieved_incl_sample_indices": with_u,
+        "frac_incl_sample_indices": with_u / HBM_PEAK_GBS,
+        "bytes_per_launch_incl_sample_indices": alg_bytes + 4 * npairs,
+    }
+
+
+DUMP_SAMPLE = 1 << 21   # forces beyond this many pairs are dumped as a fixed sample (16 MB + its 16 MB of indices)
+
+
+def dump_outputs(outdir, forces, energy):
+    """What the last timed step handed its caller, as float64 .npy files (at most ~32 MB in all)."""
+    os.makedirs(outdir, exist_ok=True)
+    index_path = os.path.join(outdir, "forces_index.npy")
+    if forces.size > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(forces.size, DUMP_SAMPLE, replace=False))
+        np.save(index_path, idx.astype(np.float64))
+        forces = forces[idx]
+    elif os.path.exists(index_path):
+        os.remove(index_path)   # (left by an earlier, sampled run into the same directory)
+    np.save(os.path.join(outdir, "forces.npy"), np.ascontiguousarray(forces, dtype=np.float64))
+    np.save(os.path.join(outdir, "energy.npy"), np.array([energy], dtype=np.float64))
 
 
 class ExtrasGuard:
@@ -587,12 +610,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--pairs", type=int, default=0, help="pairs per GPU (default W1 = 1,048,576)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (pair forces, energy) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the roofline from stamped launches, the other step "
+                         "modes and workloads, the HBM-bound capture, PCIe-inclusive steps and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-w2", action="store_true",
-                    help="skip the 38.8M-pair interpolation capture (W2 = BASELINE configs[2], the HBM-bound case)")
+                    help="(--full) skip the 38.8M-pair interpolation capture (W2 = BASELINE configs[2], the HBM-bound case)")
     ap.add_argument("--w2", action="store_true", help=argparse.SUPPRESS)  # kept for older command lines (now the default)
     ap.add_argument("--no-nd", action="store_true",
-                    help="skip the coordinate-CV section (BASELINE configs[3]/[4]: 2048^2 and 512^3 grids; part of the default line)")
+                    help="(--full) skip the coordinate-CV section (BASELINE configs[3]/[4]: 2048^2 and 512^3 grids)")
     ap.add_argument("--nd", action="store_true", help=argparse.SUPPRESS)  # kept for older command lines (now the default)
     ap.add_argument("--cpu-worker", type=float, default=0.0, help=argparse.SUPPRESS)   # (child of cpu_baseline_all_cores)
     ap.add_argument("--cpu-worker-dir", default="", help=argparse.SUPPRESS)
@@ -600,6 +628,8 @@ def main():
                     help="alternative line: STRONG scaling of the all-samples hill mode (hill_density unset; every one of "
                          "1,048,576 pair distances deposits a hill each step; the samples are split over the GPUs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_worker > 0:   # CPU only: never touches the GPU
         os.makedirs(args.cpu_worker_dir, exist_ok=True)
@@ -681,25 +711,49 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # K1's launch is stamped (dispatch begin / end timestamps) on a few steps of the timed region -- 1 of 20, 10 of 200:
-    # a stamped launch costs the stream ~15 us (an unstamped step takes ~31 us; every 4th step stamped, round 1's
-    # choice, added 3.5 us to EVERY step of the average), so a sparse sample keeps `ms_per_step` what the step costs.
+    # --full: K1's launch is stamped (dispatch begin / end timestamps) on a few steps of the timed region -- 1 of 20, 10
+    # of 200: a stamped launch costs the stream ~15 us (an unstamped step takes ~31 us; every 4th step stamped, round
+    # 1's choice, added 3.5 us to EVERY step of the average), so a sparse sample keeps `ms_per_step` what the step costs.
     # (EDM_BENCH_TIMED_EVERY overrides; the first stamped launch of a process pays for switching the queue's profiling
-    #  on -- spent here on two extra warm-up steps, outside the timed region)
+    #  on -- spent here on two extra warm-up steps, outside the timed region.  A plain run stamps nothing but takes the
+    #  same two steps, so that its timed steps compute what those of --full do.)
     n_stamps = min(10, max(1, args.steps // 20))
     TIMED_EVERY = int(os.environ.get("EDM_BENCH_TIMED_EVERY", "0")) or max(1, args.steps // n_stamps)
-    g.profile_enable(1)
+    if args.full:
+        g.profile_enable(1)
     for _ in range(2):
         step()
-    g.profile_read(reset=True)
-    g.profile_enable(TIMED_EVERY)
-    g.profile_read(reset=True)
+    if args.full:
+        g.profile_read(reset=True)
+        g.profile_enable(TIMED_EVERY)
+        g.profile_read(reset=True)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         energy = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if dist is not None:
+        import torch
+
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_f.to_host(), energy)
+    gate_giveups = b.get("ord_gate_giveups")
+    headline = headline_dict(args, world, npairs, elapsed)
+    # (the reference-order step's record and force pass run on a second stream behind a gate wave that waits for the hill
+    #  batch's limiter; a gate that gave up -- kernels of different streams run one at a time, e.g. under rocprofv3 --pmc --
+    #  sends the object back to one stream for good: 0 in an ordinary run)
+    headline["second_stream_gate_giveups"] = gate_giveups
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     k_ms, k_launches = g.profile_read(reset=True)
     # stamped tail: the same step, every launch of K1's kernel stamped and read one by one (outside the timed region --
     # a stamped launch costs the stream ~15 us)
@@ -711,22 +765,11 @@ def main():
         if l_t:
             tail_us.append(ms_t / l_t * 1e3)
     g.profile_enable(False)
-    if dist is not None:
-        import torch
-
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
 
     # Everything below is informational (component rates, the second quantity of the metric, the HBM-bound capture,
     # the CPU baseline).  The headline numbers are complete at this point: if an extra ever failed to finish -- the
     # multi-rank ones run collectives -- rank 0 still prints the line, marked, instead of losing the measurement.
-    gate_giveups = b.get("ord_gate_giveups")
-    headline = headline_dict(args, world, npairs, elapsed, k_ms, k_launches, TIMED_EVERY, tail_us)
-    # (the reference-order step's record and force pass run on a second stream behind a gate wave that waits for the hill
-    #  batch's limiter; a gate that gave up -- kernels of different streams run one at a time, e.g. under rocprofv3 --pmc --
-    #  sends the object back to one stream for good: 0 in an ordinary run)
-    headline["second_stream_gate_giveups"] = gate_giveups
+    headline["roofline"] = roofline_dict(npairs, k_ms, k_launches, TIMED_EVERY, tail_us)
     # second quantity of the metric (BASELINE.json: "... + hill-adds/sec", target: strong scaling at 8 GPUs): the
     # all-samples hill mode, 1,048,576 hills per step in total split over the GPUs (a collective: every rank runs it);
     # part of the measured line, not of the guarded extras

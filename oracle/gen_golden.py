@@ -26,6 +26,7 @@ import workloads as W  # noqa: E402
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pairfix_cases as PF  # noqa: E402  (seeded inputs shared with the tests)
+import oracle_ref_cases as RC  # noqa: E402  (the cases of tests/test_oracle_vs_ref.py)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -318,13 +319,58 @@ def gen_pairfix(lib):
     shutil.rmtree(tmp)
 
 
+# --------------------------------------------------------------------------
+# scenario 5: the cases of tests/test_oracle_vs_ref.py (grids, grid files, gaussian grids, the bias controller,
+# the config reader, the pair fix's order) -- what the reference observed, per case
+# --------------------------------------------------------------------------
+def gen_vsref(lib):
+    fixtures = os.path.join(GOLDEN, "ref_fixtures")
+    tmp = tempfile.mkdtemp(prefix="edm_golden_")
+    cwd = os.getcwd()
+    os.chdir(tmp)   # (read_test.edm names its target grid relative to the working directory)
+
+    def case_dir(name):
+        d = os.path.join(tmp, name)
+        os.makedirs(d)
+        return d
+
+    try:
+        out = dict(grid={}, grid_files={}, gauss_setup={}, gauss_lookup={}, bias={})
+        for i in range(len(RC.GRID_CASES)):
+            for deriv, interp in RC.GRID_MODES:
+                out["grid"].update(RC.pack(RC.grid_case_id(i, deriv, interp), RC.run_grid(lib, i, deriv, interp)))
+        for name, dim in RC.READ_CASES:
+            out["grid_files"].update(RC.pack(name, RC.run_grid_read_write(lib, fixtures, case_dir("rw_" + name), name, dim)))
+        out["grid_files"].update(RC.pack("add_grid", RC.run_grid_add_grid(lib, fixtures)))
+        for i in range(len(RC.GAUSS_CASES)):
+            out["gauss_setup"].update(RC.pack("case%d" % i, RC.run_gauss_setup(lib, i)))
+            out["gauss_lookup"].update(RC.pack("case%d" % i, RC.run_gauss_add_lookup(lib, i)))
+        for name in sorted(RC.BIAS_CFGS):
+            out["bias"].update(RC.pack(name, RC.run_bias(lib, name, case_dir("bias_" + name))))
+        out["bias"].update(RC.pack("config_reader", RC.run_config_reader(lib, fixtures, tmp)))
+        for seed in RC.PAIR_FIX_SEEDS:
+            out["bias"].update(RC.pack("pair_fix_seed%d" % seed, RC.run_pair_fix(lib, case_dir("pf%d" % seed), seed)))
+    finally:
+        os.chdir(cwd)
+        shutil.rmtree(tmp)
+    for kind, arrays in out.items():
+        np.savez_compressed(RC.golden_path(GOLDEN, kind), **arrays)
+
+
+SECTIONS = dict(gauss=gen_gauss, controller=gen_controller, kats_and_files=gen_kats_and_files, pairfix=gen_pairfix,
+                vsref=gen_vsref)
+
+
 def main():
+    """python oracle/gen_golden.py [section ...]  (default: every section)"""
+    names = sys.argv[1:] or list(SECTIONS)
+    unknown = [n for n in names if n not in SECTIONS]
+    if unknown:
+        raise SystemExit("unknown section(s) %s; known: %s" % (unknown, " ".join(SECTIONS)))
     lib = B.load("ref")
     os.makedirs(GOLDEN, exist_ok=True)
-    gen_gauss(lib)
-    gen_controller(lib)
-    gen_kats_and_files(lib)
-    gen_pairfix(lib)
+    for n in names:
+        SECTIONS[n](lib)
     print("golden fixtures written to", GOLDEN)
 
 

@@ -4,9 +4,9 @@ box by tools/profile_capture.sh) into the tracked summaries under profiles/:
     python profiles/summarize.py gpurun_out/p2 r02
 
 Commands that produced the inputs (tools/profile_capture.sh, run through gpurun):
-  rocprofv3 --kernel-trace --stats --output-format csv -d <dir>/trace     -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d <dir>/pmc_fetch       -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d <dir>/pmc_write       -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
+  rocprofv3 --kernel-trace --stats --output-format csv -d <dir>/trace     -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d <dir>/pmc_fetch       -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d <dir>/pmc_write       -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d <dir>/cal_fetch       -- tools/randline 16 2097152 4
 Counter units and the gfx950 correction follow /opt/skills/guides/MI355X_MICROARCH.md (HBM section):
 FETCH_SIZE / WRITE_SIZE are in KiB; FETCH_SIZE reports exactly half of a wide coalesced (16 B/lane)
@@ -37,7 +37,7 @@ def main():
         per[key].append((int(r["Start_Timestamp"]), (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3))
     per = {k: [d for _, d in sorted(v)] for k, v in per.items()}   # launch order
     summary = {"kernels": [], "pmc": {}}
-    # the trace command runs `--warmup 5 --steps 50`: bench.py runs 5 warm-up steps, 2 more that switch the queue's
+    # the trace command runs `--full --warmup 5 --steps 50`: bench.py runs 5 warm-up steps, 2 more that switch the queue's
     # profiling on, then the 50 steps of the timed region: launches 8..57 of each kernel of the reference-order step
     warmup, steps = 7, 50
     for (name, grid, wg), v in sorted(per.items(), key=lambda kv: -sum(kv[1])):

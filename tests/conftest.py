@@ -22,18 +22,6 @@ def oracle_lib():
     return binding.load("oracle")
 
 
-@pytest.fixture(scope="session")
-def ref_lib():
-    """The real reference, built from /root/reference by oracle/Makefile (present in
-    the build container; on the GPU box only if the prebuilt .so travelled)."""
-    from oracle import binding
-
-    try:
-        return binding.load("ref")
-    except (FileNotFoundError, OSError, Exception) as exc:  # noqa: BLE001
-        pytest.skip("reference build oracle/_ref/libedm_ref.so unavailable: %s" % exc)
-
-
 @pytest.fixture()
 def workdir(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)

@@ -1,10 +1,12 @@
 """bench.py's output contract (the driver parses it): ONE JSON line on stdout with the agreed keys, the metric of
-BASELINE.json, a roofline object for the dominant kernel.  Runs the real benchmark with a handful of steps."""
+BASELINE.json; with --full also a roofline object for the dominant kernel and the other measurements.  Runs the real
+benchmark with a handful of steps."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                          "--no-cpu-baseline", "--no-w2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--no-cpu-baseline", "--no-w2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, "exactly one line on stdout: %r" % lines[:5]
@@ -62,6 +64,39 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
         assert st["min_ms"] <= st["median_ms"] <= st["max_ms"] and st["poll_fallbacks"] >= 0 and st["replica_rebuilds"] >= 0
         assert c["pcie_inclusive_step"]["ms_per_step"] > c["step_ms"]
     assert d["pcie_inclusive"]["ms_per_step"] > d["ms_per_step"]
+
+
+def _plain_run(outdir):
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                          "--dump-outputs", str(outdir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, "exactly one line on stdout: %r" % lines[:5]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_one(tmp_path):
+    """Without --full the line is the headline alone; --steps sets the timed steps; --dump-outputs writes the last timed
+    step's forces and energy, the same (to summation order) from run to run with the same arguments."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _plain_run(a)
+    assert "evals/sec" in d["metric"] and d["unit"] == "million evals/s" and d["value"] > 0
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["ms_per_step"] > 0
+    assert d["higher_is_better"] is True and d["dtype"] == "f64"
+    pairs = d["config"]["pairs_per_gpu"] * d["n_gpus"]
+    assert abs(d["value"] - pairs / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * d["value"]
+    for key in ("roofline", "hill_adds_strong_scaling", "step_modes", "coordinate_cv", "pcie_inclusive", "cpu_baseline"):
+        assert key not in d, "%s is measured under --full only" % key
+    assert sorted(os.listdir(a)) == ["energy.npy", "forces.npy"]
+    assert sum(os.path.getsize(a / n) for n in os.listdir(a)) <= 64 << 20
+    fa, ea = np.load(a / "forces.npy"), np.load(a / "energy.npy")
+    assert fa.dtype == np.float64 and fa.shape == (d["config"]["pairs_per_gpu"],) and np.isfinite(fa).all() and fa.any()
+    assert ea.dtype == np.float64 and ea.shape == (1,) and np.isfinite(ea).all()
+    _plain_run(b)
+    fb, eb = np.load(b / "forces.npy"), np.load(b / "energy.npy")
+    assert np.allclose(fb, fa, rtol=1e-12, atol=1e-12 * np.abs(fa).max())
+    assert np.allclose(eb, ea, rtol=1e-12, atol=0)
 
 
 def test_gpus_flag_without_launcher_never_reports_a_smaller_job():
