@@ -12,7 +12,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -131,20 +130,12 @@ struct DeltaAddJob {
   int dim = 1, f_stride = 1, pieces = 1;
   hipEvent_t *ev = nullptr;
 };
-static double g_add_trace[64][4];   // development aid (EDM_HIP_TRACE=step_host): per thread, woken / first piece seen / waited / done
-static double trace_now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static int delta_add_pieces(const DeltaAddJob &j, int me, int threads) {
-  g_add_trace[me][0] = trace_now_us();
-  g_add_trace[me][2] = 0;
   // every thread takes its share of EVERY piece: the copies stay few and large (the link's rate), the add of a piece is
   // spread over the threads
   for (int c = 0; c < j.pieces; c++) {
     const long long p0 = c * j.per, p1 = (p0 + j.per < j.n) ? p0 + j.per : j.n;
-    const double tw = trace_now_us();
     hipError_t e = hipEventSynchronize(j.ev[c]);
-    g_add_trace[me][2] += trace_now_us() - tw;
-    if (c == 0) g_add_trace[me][1] = trace_now_us();
-    g_add_trace[me][3] = 0;
     if (e != hipSuccess) return (int)e;
     if (p0 >= p1) continue;
     const long long share = (p1 - p0 + threads - 1) / threads;
@@ -162,7 +153,6 @@ static int delta_add_pieces(const DeltaAddJob &j, int me, int threads) {
         for (int d = 0; d < j.dim; d++) j.h_f[(size_t)i * j.f_stride + d] += j.dl[(size_t)i * j.dim + d];
     }
   }
-  g_add_trace[me][3] = trace_now_us();
   return 0;
 }
 class DeltaAddPool {
@@ -1254,7 +1244,6 @@ static int process_new_hills(edm_hip_bias *b, long long n, const double *d_x, in
         }
       }
       bb->ord_early.done = true;
-      ht_mark(bb->bias, 9);
     };
   }
   int rc = apply_hills(b->bias, spec, &oc, false);
@@ -1477,10 +1466,6 @@ int edm_hip_bias_pair_step(edm_hip_bias *b, long long n, const double *d_r, doub
     set_error("pair_step: the pair-distance CV is 1-D (fix_edm_pair.cpp:52)");
     return EDM_HIP_ERR_ARG;
   }
-  static const bool host_trace = getenv("EDM_HIP_TRACE") != nullptr;
-  static double last_exit_us = 0;
-  const double t_in = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  if (host_trace && b->bias) b->bias->ht_ref_us = t_in;
   // pre_add_hill first, as fix_edm_pair does (:174): a pending overflow flush is part of the bias the
   // forces see
   int rc = do_pre_add_hill(b, est_hill_count < 0 ? n_samples : est_hill_count);
@@ -1489,7 +1474,6 @@ int edm_hip_bias_pair_step(edm_hip_bias *b, long long n, const double *d_r, doub
     if (n > 0) EDM_HIP_TRY(hipMemset(d_force, 0, sizeof(double) * (size_t)n));
     return do_post_add_hill(b);
   }
-  ht_mark(b->bias, 0);
   // forces (queued, not waited for), then the new hills behind them on the same stream: one host wait
   // (where the step's selection runs as a chained launch, the force kernel rides in that launch)
   b->pending = PendingForces();
@@ -1501,7 +1485,6 @@ int edm_hip_bias_pair_step(edm_hip_bias *b, long long n, const double *d_r, doub
     b->pending.d_force = d_force;
   }
   rc = process_new_hills(b, n_samples, d_sample_r, 1, d_runiform, -1);
-  ht_mark(b->bias, 7);
   // (no hills this step, or they were skipped: the force kernel goes alone -- with tagged partial sums the host can
   //  look at instead of waiting for the stream, see edm_hip_gauss_pair_forces)
   unsigned long long tag = 0;
@@ -1520,20 +1503,7 @@ int edm_hip_bias_pair_step(edm_hip_bias *b, long long n, const double *d_r, doub
     for (int k = 0; k < b->pending.nblk; k++) e += b->bias->h_partials[(tag && b->pending.tagged) ? 2 * k : k];
   }
   if (energy) *energy = e;
-  ht_mark(b->bias, 8);
   rc = do_post_add_hill(b);
-  if (host_trace) {
-    const double t_out = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    if (b->bias->ready_seq == 160) {
-      fprintf(stderr, "[edm host] pair_step: %.2f us inside the call, %.2f us since the previous call returned\n", t_out - t_in,
-              t_in - last_exit_us);
-      const double *m = b->bias->ht_marks;
-      fprintf(stderr, "[edm host] marks (us after entry): pre_add_hill done %.2f | first launch %.2f -> %.2f | second launch %.2f -> %.2f | "
-              "poll %.2f -> %.2f | new hills processed %.2f | energy summed %.2f | exit %.2f\n", m[0], m[1], m[2], m[3], m[4], m[5], m[6],
-              m[7], m[8], t_out - t_in);
-    }
-    last_exit_us = t_out;
-  }
   return rc;
 }
 
@@ -1627,34 +1597,7 @@ static int ordered_records_enqueue(edm_hip_bias *b, OrderedForcesArgs *out) {
   } else {
     a.dirty_seq = ++b->ord_seq;
   }
-  // development aid (EDM_HIP_TRACE=ordered): stamps of the 100th record pass to stderr
-  static const bool tracing = getenv("EDM_HIP_TRACE") && !strcmp(getenv("EDM_HIP_TRACE"), "ordered");
-  const size_t trace_wgs = (size_t)((g->g.n[0] + 31) / 32);
-  if (tracing && b->ord_seq == 100) {
-    EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a.trace), trace_wgs * 64));
-    EDM_HIP_TRY(hipMemset(a.trace, 0, trace_wgs * 64));
-  }
   EDM_HIP_TRY(launch_ordered_records(g->g, g->tables(), a, b->ord_on_own_stream ? b->ord_stream : g->stream));
-  if (a.trace) {
-    EDM_HIP_TRY(hipStreamSynchronize(b->ord_on_own_stream ? b->ord_stream : g->stream));
-    std::vector<unsigned long long> tr(trace_wgs * 8);
-    EDM_HIP_TRY(hipMemcpy(tr.data(), a.trace, trace_wgs * 64, hipMemcpyDeviceToHost));
-    (void)hipFree(a.trace);
-    a.trace = nullptr;
-    unsigned long long t0 = ~0ull;
-    for (size_t w = 0; w < trace_wgs; w++) if (tr[w * 8] && tr[w * 8] < t0) t0 = tr[w * 8];
-    const char *names[7] = {"start", "node terms done", "chunk 0 listed", "chunk 0 terms", "chunk 0 run", "chunk 0 stored", "end"};
-    for (int k = 0; k < 7; k++) {
-      std::vector<double> v;
-      for (size_t w = 0; w < trace_wgs; w++) if (tr[w * 8 + k]) v.push_back((double)(tr[w * 8 + k] - t0) * 0.01);
-      if (v.empty()) continue;
-      std::sort(v.begin(), v.end());
-      fprintf(stderr, "[edm trace] records %-16s n=%4zu  min %6.2f  med %6.2f  max %6.2f us\n", names[k], v.size(), v.front(), v[v.size() / 2], v.back());
-    }
-    unsigned long long mx = 0, sum = 0;
-    for (size_t w = 0; w < trace_wgs; w++) { sum += tr[w * 8 + 7]; if (tr[w * 8 + 7] > mx) mx = tr[w * 8 + 7]; }
-    fprintf(stderr, "[edm trace] records: hills listed per tile in chunk 0: mean %.1f max %llu (of %lld hills)\n", (double)sum / trace_wgs, mx, nh);
-  }
   *out = a;
   return EDM_HIP_OK;
 }
@@ -1678,32 +1621,7 @@ static int ordered_forces_enqueue(edm_hip_bias *b) {
   a.force = b->ord_early.d_force;
   hipEvent_t e0, e1;
   profile_slot(g, &e0, &e1);
-  // development aid (EDM_HIP_TRACE=k1o): stamps of the 100th force pass to stderr
-  static const bool tracing = getenv("EDM_HIP_TRACE") && !strcmp(getenv("EDM_HIP_TRACE"), "k1o");
-  const size_t trace_wgs = 65536;
-  if (tracing && b->ord_seq == 100) {
-    EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a.trace), trace_wgs * 64));
-    EDM_HIP_TRY(hipMemset(a.trace, 0, trace_wgs * 64));
-  }
   EDM_HIP_TRY(launch_pair_forces_ordered(g->g, a, g->d_partials, s, &b->ord_early.nblk, b->ord_early.tag, e0, e1));
-  if (a.trace) {
-    EDM_HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> tr(trace_wgs * 8);
-    EDM_HIP_TRY(hipMemcpy(tr.data(), a.trace, trace_wgs * 64, hipMemcpyDeviceToHost));
-    (void)hipFree(a.trace);
-    a.trace = nullptr;
-    unsigned long long t0 = ~0ull;
-    for (size_t w = 0; w < trace_wgs; w++) if (tr[w * 8] && tr[w * 8] < t0) t0 = tr[w * 8];
-    const char *names[5] = {"start", "hills staged", "rows staged", "first trip done", "last trip done"};
-    for (int k = 0; k < 5; k++) {
-      std::vector<double> v;
-      for (size_t w = 0; w < trace_wgs; w++) if (tr[w * 8 + k]) v.push_back((double)(tr[w * 8 + k] - t0) * 0.01);
-      if (v.empty()) continue;
-      std::sort(v.begin(), v.end());
-      fprintf(stderr, "[edm trace] k1o %-16s n=%4zu  min %6.2f  p25 %6.2f  med %6.2f  p75 %6.2f  max %6.2f us\n", names[k], v.size(),
-              v.front(), v[v.size() / 4], v[v.size() / 2], v[3 * v.size() / 4], v.back());
-    }
-  }
   return EDM_HIP_OK;
 }
 
@@ -1749,7 +1667,6 @@ static int pair_step_ordered_device(edm_hip_bias *b, long long n, const double *
   b->ord_early.tag = tag0;
   b->ord_early.armed = n > 0;
   rc = process_new_hills(b, n_samples, d_sample_r, 1, d_runiform, -1);
-  ht_mark(g, 7);
   b->ord_early.armed = false;
   b->ord_step_active = false;
   b->ord_snap_pending = false;   // (no hill batch was applied: nobody needs the copy)
@@ -1821,32 +1738,15 @@ int edm_hip_bias_pair_step_ordered(edm_hip_bias *b, long long n, const double *d
   }
   if (n < 0) n = 0;
   if (n_samples < 0) n_samples = 0;
-  static const bool host_trace = getenv("EDM_HIP_TRACE") != nullptr;   // development aid: the call's host-side marks
-  static double last_exit_us = 0;
-  const double t_in = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  if (host_trace && b->bias) b->bias->ht_ref_us = t_in;
   int rc = do_pre_add_hill(b, est_hill_count < 0 ? n_samples : est_hill_count);
   if (rc) return rc;
   if (b->b_outofbounds) {
     if (n > 0) EDM_HIP_TRY(hipMemset(d_force, 0, sizeof(double) * (size_t)n));
     return do_post_add_hill(b);
   }
-  ht_mark(b->bias, 0);
   rc = pair_step_ordered_device(b, n, d_r, d_force, d_first_sample, n_samples, d_sample_r, d_runiform, energy);
   if (rc) return rc;
-  ht_mark(b->bias, 8);
   rc = do_post_add_hill(b);
-  if (host_trace) {
-    const double t_out = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    if (b->bias->ready_seq == 160) {
-      const double *m = b->bias->ht_marks;
-      fprintf(stderr, "[edm host] pair_step_ordered: %.2f us inside the call, %.2f us since the previous call returned\n"
-              "[edm host] marks (us after entry): pre_add_hill done %.2f | selection launch %.2f -> %.2f | hill batch launch %.2f -> %.2f | "
-              "force pass queued %.2f, poll %.2f -> %.2f | new hills processed %.2f | forces seen complete %.2f | exit %.2f\n",
-              t_out - t_in, t_in - last_exit_us, m[0], m[1], m[2], m[3], m[4], m[9], m[5], m[6], m[7], m[8], t_out - t_in);
-    }
-    last_exit_us = t_out;
-  }
   return rc;
 }
 
@@ -2055,7 +1955,6 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
     return rc ? rc : do_post_add_hill(b);
   }
   hipStream_t s = b->bias->stream;
-  const double t_entry = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
   const size_t xcount = n > 0 ? (size_t)(n - 1) * (size_t)x_stride + (size_t)dim : 0;
   EDM_HIP_TRY(b->hs_x.reserve(xcount > 0 ? xcount : 1));
   EDM_HIP_TRY(b->hs_f.reserve((size_t)(n > 0 ? n : 1) * dim));
@@ -2101,10 +2000,6 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
       EDM_HIP_TRY(hipMemcpyAsync(b->hs_u.p, h_runiform, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     }
   }
-  static const bool host_trace = getenv("EDM_HIP_TRACE") && strcmp(getenv("EDM_HIP_TRACE"), "step_host") == 0;
-  auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tr[4 + MAX_PIECES] = {0};
-  if (host_trace) tr[1] = now_us();
   const int *saved_mask = b->d_mask;
   if (apply_mask >= 0) b->d_mask = b->hs_mask.p;
   DeltaCopy dc{b, n, dim, PIECES, 0, false};
@@ -2121,7 +2016,6 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
   }
   b->d_mask = saved_mask;
   if (rc) return rc;
-  if (host_trace) tr[2] = now_us();
   if (n > 0) {
     delta_copy_queue(&dc);   // (forces only, or a step that never launched them through the hook: now)
     if (dc.rc) {
@@ -2149,17 +2043,6 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
   // (success: the step's completion record is behind the uploads on the main stream, every piece's event has been
   //  waited for on the copy stream -- nothing of the caller's is in flight, no stream wait needed: ~17 us each)
   guard.armed = false;
-  if (host_trace) {   // development aid: the call's host marks, us since entry
-    const double t_added = now_us();
-    (void)hipStreamSynchronize(b->copy_stream);
-    const double t_copy = now_us();
-    (void)hipStreamSynchronize(s);
-    fprintf(stderr, "[edm trace] step_host: uploads queued %.1f  step returned %.1f  delta added %.1f (%d pieces, %d threads)  copy stream idle %.1f  main stream idle %.1f\n",
-            tr[1] - t_entry, tr[2] - t_entry, t_added - t_entry, PIECES, b->add_pool.threads(), t_copy - t_entry, now_us() - t_entry);
-    for (int t = 0; t < b->add_pool.threads(); t++)
-      fprintf(stderr, "[edm trace]   add thread %d: started %.1f  first piece seen %.1f  waited %.1f in all  done %.1f\n", t,
-              g_add_trace[t][0] - t_entry, g_add_trace[t][1] - t_entry, g_add_trace[t][2], g_add_trace[t][3] - t_entry);
-  }
   return EDM_HIP_OK;
 }
 

@@ -24,7 +24,6 @@ namespace edm {
 
 static constexpr long long EDM_TAG_CAP_HOST = 1024;   // = EDM_TAG_CAP of edm_kernels.hip
 
-// development aid (EDM_HIP_TRACE): host clock, microseconds after the traced step's entry, at marked place `slot`
 // EDM_HIP_TEST_FORCE=<token>[,<token>...] in the environment (tests only): sends work down the paths production
 // reaches only under other conditions -- long lists, grids without a ball list, batches that cannot be fused -- so
 // that they stay covered.  Tokens: no_ball_list, no_lookup_prep, no_tagged_integrals, no_fast_header,
@@ -42,12 +41,6 @@ long long test_force_value(const char *key) {
   const size_t at = env.find(std::string(",") + key + "=");
   return at == std::string::npos ? 0 : atoll(env.c_str() + at + strlen(key) + 2);
 }
-void ht_mark(edm_hip_gauss *g, int slot) {
-  static const bool on = getenv("EDM_HIP_TRACE") != nullptr;
-  if (!on || !g || slot < 0 || slot >= 12) return;
-  g->ht_marks[slot] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() - g->ht_ref_us;
-}
-
 
 static thread_local std::string g_last_error;
 
@@ -1239,43 +1232,7 @@ int pending_forces_flush(const edm_hip_gauss *g, PendingForces *pf) {
   if (!rc) pf->launched();
   return rc;
 }
-int select_prep_enqueue(const edm_hip_gauss *g, const SelectArgs &a_in, const HillList &h, PendingForces *pf) {
-  SelectArgs a = a_in;
-  // development aid (EDM_HIP_TRACE=select): stamps of one k_pair_forces_select launch to stderr
-  static const bool tracing = getenv("EDM_HIP_TRACE") && !strcmp(getenv("EDM_HIP_TRACE"), "select");
-  static int launches = 0;
-  unsigned long long *d_trace = nullptr;
-  size_t trace_wgs = 0;
-  if (tracing && pf && pf->active && !pf->list && ++launches == 150) {
-    trace_wgs = (size_t)((a.n + 2047) / 2048) + 1024;
-    if (hipMalloc(reinterpret_cast<void **>(&d_trace), trace_wgs * 64) == hipSuccess) {
-      (void)hipMemset(d_trace, 0, trace_wgs * 64);
-      a.trace = d_trace;
-    }
-  }
-  struct TraceDump {
-    const edm_hip_gauss *g; unsigned long long *d; size_t wgs, nsel;
-    ~TraceDump() {
-      if (!d) return;
-      (void)hipStreamSynchronize(g->stream);
-      std::vector<unsigned long long> tr(wgs * 8);
-      (void)hipMemcpy(tr.data(), d, wgs * 64, hipMemcpyDeviceToHost);
-      (void)hipFree(d);
-      unsigned long long t0 = ~0ull;
-      for (size_t w = 0; w < wgs; w++) if (tr[w * 8] && tr[w * 8] < t0) t0 = tr[w * 8];
-      const char *names[8] = {"start", "published", "ticket (not last)", "ticket (last)", "list prepared", "", "", "end"};
-      for (int role = 0; role < 2; role++)
-        for (int k = 0; k < 8; k++) {
-          std::vector<double> v;
-          for (size_t w = role ? nsel : 0; w < (role ? wgs : nsel); w++)
-            if (tr[w * 8 + k]) v.push_back((double)(tr[w * 8 + k] - t0) * 0.01);
-          if (v.empty()) continue;
-          std::sort(v.begin(), v.end());
-          fprintf(stderr, "[edm trace] %s %-18s n=%4zu  min %6.2f  med %6.2f  max %6.2f us\n", role ? "forces   " : "selection",
-                  names[k], v.size(), v.front(), v[v.size() / 2], v.back());
-        }
-    }
-  } dump{g, d_trace, trace_wgs, (size_t)((a.n + 2047) / 2048)};
+int select_prep_enqueue(const edm_hip_gauss *g, const SelectArgs &a, const HillList &h, PendingForces *pf) {
   if (pf && pf->active && pf->list && g->g.dim == 1 && a.n > 0 && pf->pl.nall > 0) {
     pf->active = false;
     EDM_HIP_TRY(launch_pairlist_forces_select(a, g->g, h, g->rec, pf->pl, g->d_partials, g->stream, &pf->nblk));
@@ -1301,18 +1258,14 @@ int select_prep_enqueue(const edm_hip_gauss *g, const SelectArgs &a_in, const Hi
     hipEvent_t e0, e1;
     profile_slot(g, &e0, &e1);
     pf->active = false;
-    ht_mark(const_cast<edm_hip_gauss *>(g), 1);
     EDM_HIP_TRY(launch_pair_forces_select(a, g->g, h, g->rec, pf->n, pf->d_r, pf->d_force, g->d_partials, g->stream, e0, e1,
                                           &pf->nblk));
     pf->launched();
-    ht_mark(const_cast<edm_hip_gauss *>(g), 2);
     return EDM_HIP_OK;
   }
   int rc = pending_forces_flush(g, pf);
   if (rc) return rc;
-  ht_mark(const_cast<edm_hip_gauss *>(g), 1);
   EDM_HIP_TRY(launch_select_prep(a, g->g, h, g->stream));
-  ht_mark(const_cast<edm_hip_gauss *>(g), 2);
   return EDM_HIP_OK;
 }
 // forces-only calls poll their workgroups' tagged sums unless EDM_HIP_POLL=0
@@ -1852,14 +1805,6 @@ int apply_hills(edm_hip_gauss *g, const ApplySpec &spec, ApplyOutcome *out, bool
       la.ready_flag = g->d_ready;
       la.ready_seq = ++g->ready_seq;
       la.early_word = 1;
-      static const bool tracing = getenv("EDM_HIP_TRACE") != nullptr;   // development aid: stamps of one launch to stderr
-      const size_t trace_wgs = (size_t)nh + (size_t)((q.n[0] + 31) / 32);
-      unsigned long long *d_trace = nullptr;
-      if (tracing && g->ready_seq == 150) {
-        EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_trace), trace_wgs * 64));
-        EDM_HIP_TRY(hipMemset(d_trace, 0, trace_wgs * 64));
-        la.trace = d_trace;
-      }
       PostSpec ps;
       ps.ticket = g->d_tickets + 2 * EDM_TICKET_INTS;
       ps.hist_geom = spec.hist_g;
@@ -1876,7 +1821,6 @@ int apply_hills(edm_hip_gauss *g, const ApplySpec &spec, ApplyOutcome *out, bool
         ps.rb_bytes = (long long)rb_bytes;
         rb_pushed = true;
       }
-      ht_mark(g, 3);
       if (spec.ord_terms && !spec.flush_mode) {   // (a reference-order step: the launch also stores the hills' stencil terms)
         la.ord_terms = spec.ord_terms;
         la.ord_dirty = spec.ord_dirty;
@@ -1888,65 +1832,14 @@ int apply_hills(edm_hip_gauss *g, const ApplySpec &spec, ApplyOutcome *out, bool
       }
       EDM_HIP_TRY(launch_integrals_gather(q, tabs, g->rec, hl, spec.d_h, spec.h_const, p_added, la, hh, plan, g->d_dirty, s,
                                           chain_post ? &ps : nullptr));
-      ht_mark(g, 4);
       gather_done = true;
-      if (d_trace) {
-        EDM_HIP_TRY(hipStreamSynchronize(s));
-        std::vector<unsigned long long> tr(trace_wgs * 8);
-        EDM_HIP_TRY(hipMemcpy(tr.data(), d_trace, trace_wgs * 64, hipMemcpyDeviceToHost));
-        (void)hipFree(d_trace);
-        unsigned long long t0 = ~0ull;
-        for (size_t w = 0; w < trace_wgs; w++)
-          if (tr[w * 8] && tr[w * 8] < t0) t0 = tr[w * 8];
-        const char *names_i[8] = {"start", "integral done", "last wg: ticket", "flag published", "host copy done", "", "", "end"};
-        const char *names_g[8] = {"start", "terms parked", "flag seen", "", "", "", "body end", "post end"};
-        for (int role = 0; role < 2; role++) {
-          for (int k = 0; k < 8; k++) {
-            std::vector<double> v;
-            for (size_t w = role ? (size_t)nh : 0; w < (role ? trace_wgs : (size_t)nh); w++)
-              if (tr[w * 8 + k]) v.push_back((double)(tr[w * 8 + k] - t0) * 0.01);
-            if (v.empty()) continue;
-            std::sort(v.begin(), v.end());
-            fprintf(stderr, "[edm trace] %s %-16s n=%4zu  min %6.2f  med %6.2f  max %6.2f us\n", role ? "gather   " : "integrals",
-                    role ? names_g[k] : names_i[k], v.size(), v.front(), v[v.size() / 2], v.back());
-          }
-        }
-      }
     } else {
-      static const bool tracing_nd = getenv("EDM_HIP_TRACE") != nullptr;   // development aid: stamps of one launch to stderr
-      static int traced_launches = 0;
-      unsigned long long *d_trace = nullptr;
-      if (tracing_nd && ++traced_launches >= 40 && traced_launches <= 43) {
-        EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_trace), (size_t)nh * 64));
-        EDM_HIP_TRY(hipMemset(d_trace, 0, (size_t)nh * 64));
-        la.trace = d_trace;
-      }
       // a culled gather follows (2-D / 3-D, short list on a big grid): its tile list is built by extra workgroups of
       // this launch instead of a launch of its own (the list needs the prepared hills, nothing of the integrals)
       MarkArgs mark{plan.tile_flags, plan.tile_list, ntiles, plan.tile_parity};
       const bool mark_here = dim > 1 && plan.tile_flags && plan.tile_list && plan.groups == 1 && !sharded && !fused && !spec.ordered;
       EDM_HIP_TRY(launch_hill_integrals(q, tabs, hl, spec.d_h, spec.h_const, p_added, s, &la, mark_here ? &mark : nullptr));
       if (mark_here) plan.tiles_marked = 1;
-      if (d_trace) {
-        EDM_HIP_TRY(hipStreamSynchronize(s));
-        std::vector<unsigned long long> tr((size_t)nh * 8);
-        EDM_HIP_TRY(hipMemcpy(tr.data(), d_trace, (size_t)nh * 64, hipMemcpyDeviceToHost));
-        (void)hipFree(d_trace);
-        unsigned long long t0 = ~0ull;
-        for (size_t w = 0; w < (size_t)nh; w++)
-          if (tr[w * 8] && tr[w * 8] < t0) t0 = tr[w * 8];
-        const char *names_i[8] = {"start", "integral done", "last wg: ticket", "", "limiter stage done", "walk begins", "", "end"};
-        fprintf(stderr, "[edm trace] k_hill_integrals<%d>, launch bound %lld hills, flush %d\n", dim, nh, spec.flush_mode);
-        for (int k = 0; k < 8; k++) {
-          std::vector<double> v;
-          for (size_t w = 0; w < (size_t)nh; w++)
-            if (tr[w * 8 + k]) v.push_back((double)(tr[w * 8 + k] - t0) * 0.01);
-          if (v.empty()) continue;
-          std::sort(v.begin(), v.end());
-          fprintf(stderr, "[edm trace] integrals %-18s n=%4zu  min %6.2f  med %6.2f  max %6.2f us\n", names_i[k], v.size(), v.front(),
-                  v[v.size() / 2], v.back());
-        }
-      }
     }
   } else if (spec.limited || want_total) {
     EDM_HIP_TRY(launch_hill_integrals(q, tabs, hl, spec.d_h, spec.h_const, p_added, s));
@@ -2090,12 +1983,9 @@ int apply_hills(edm_hip_gauss *g, const ApplySpec &spec, ApplyOutcome *out, bool
   bool plain_fast = false;
   LimitResult header_res;
   memset(&header_res, 0, sizeof(header_res));
-  static const bool host_trace = getenv("EDM_HIP_TRACE") != nullptr;   // development aid: host-side stamps
   if (spec.before_wait)
     spec.before_wait(spec.before_wait_ctx, base_heights, ws.tail_h1.p, p_h2, dres, out ? out->terms_emitted : false,
                      hook_ready_flag, hook_ready_seq, spec.d_nh);
-  const auto ht_before_poll = std::chrono::steady_clock::now();
-  ht_mark(g, 5);
   if (polled) {
     // the limiter's workgroup flags the host-mapped region once it is complete: poll the word instead of waiting
     // for the stream's completion signal (bounded; falls back to the stream wait)
@@ -2152,13 +2042,6 @@ int apply_hills(edm_hip_gauss *g, const ApplySpec &spec, ApplyOutcome *out, bool
   } else {
     EDM_HIP_TRY(hipStreamSynchronize(s));
   }
-  if (host_trace && g->ready_seq == 160) {
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[edm host] apply_hills: polling took %.2f us (entered the poll %.2f us after a reference point)\n",
-            std::chrono::duration<double, std::micro>(now - ht_before_poll).count(),
-            std::chrono::duration<double, std::micro>(ht_before_poll.time_since_epoch()).count() - g->ht_ref_us);
-  }
-  ht_mark(g, 6);
   long long nh_act = nh;
   if (spec.limited) {
     res = plain_fast ? header_res : *hres;

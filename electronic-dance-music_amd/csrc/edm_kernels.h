@@ -178,7 +178,6 @@ struct OrderedForcesArgs {
   const int *first_sample;  // [n] sample index of pair k's first add_hill call, or NULL: 2 k (the virtual samples of a
                             // device-resident neighbour list)
   double *force;            // [n] out: -dV/dr
-  unsigned long long *trace;   // development aid (EDM_HIP_TRACE=ordered): 8 wall-clock stamps per workgroup of the record pass, or NULL
 };
 size_t ordered_record_doubles(const Geom &g, long long nh_cap);
 size_t ordered_count_shorts(const Geom &g, long long nh_cap);
@@ -282,7 +281,6 @@ struct SelectArgs {
   int *ticket;            // zero-initialised device int, left at zero
   double *pack;           // multi-GPU: instead of sel/prep, write this rank's exchange packet
                           // [count, x_0 .. x_{bound-1}] (bound = h.nh, dim doubles per position)
-  unsigned long long *trace;   // development aid (EDM_HIP_TRACE): 8 wall-clock stamps per workgroup of k_pair_forces_select, or NULL
   // reference-order pair step: the step-start copy of the 1-D grid's records rides in this launch (nothing has touched
   // the grid yet: the hills are applied by a later launch); snap_n 16-byte records, or snap_dst == NULL
   const double *snap_src;
@@ -512,8 +510,6 @@ struct LimitArgs {
   // leaves 0 = integrals first, so callers set it), 0 / 1 = forced (tests)
   int shared_device;
   int tiles_first_mode;
-  // development aid (EDM_HIP_TRACE=1): 8 wall-clock stamps (10 ns units) per workgroup of k_integrals_gather, or NULL
-  unsigned long long *trace;
 };
 bool hill_integrals_can_chain_limit(long long nh);
 // boundary duplication + histogram chained onto the gather (plan.groups == 1, hh.res_dev and h.hx0 set)

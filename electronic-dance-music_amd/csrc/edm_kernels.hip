@@ -1932,12 +1932,7 @@ __device__ __forceinline__ void select_prep_body(const SelectArgs &a, const Geom
       if (threadIdx.x == 0) publish(&a.counts[bid], run);
     }
   }
-  if (a.trace && threadIdx.x == 0) a.trace[(size_t)bid * 8 + 1] = wall_clock64();
-  if (!last_block_done(a.ticket, nblk, bid)) {
-    if (a.trace && threadIdx.x == 0) a.trace[(size_t)bid * 8 + 2] = wall_clock64();
-    return;
-  }
-  if (a.trace && threadIdx.x == 0) a.trace[(size_t)bid * 8 + 3] = wall_clock64();
+  if (!last_block_done(a.ticket, nblk, bid)) return;
 
   // scan of the per-workgroup counts: every thread takes PERC consecutive workgroups and requests their
   // counts together (one memory round trip per BLOCK * PERC workgroups; 512 workgroups = one pass), the
@@ -2002,7 +1997,6 @@ __device__ __forceinline__ void select_prep_body(const SelectArgs &a, const Geom
     if (threadIdx.x == 0) s_carry = carry + pass_total;
     __syncthreads();
   }
-  if (a.trace && threadIdx.x == 0) a.trace[(size_t)bid * 8 + 4] = wall_clock64();
   if (threadIdx.x == 0) {
     const long long total = s_carry;
     *a.count_host = total;
@@ -2069,13 +2063,11 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_select(SelectArgs a, Geom
   extern __shared__ double2 lds_all[];
   // role of this workgroup: selection workgroup `sb` (sb < nsel) or K1 workgroup `sb - nsel`
   const unsigned sb = f.sel_first ? blockIdx.x : (blockIdx.x >= f.nk1 ? blockIdx.x - f.nk1 : f.nsel + blockIdx.x);
-  if (a.trace && threadIdx.x == 0) a.trace[(size_t)sb * 8] = wall_clock64();   // (trace slots: selection first, then K1)
   if (sb < f.nsel)
     select_prep_body<1>(a, g, h, sb, f.nsel);
   else
     pair_forces_fast_body<false, BLOCK>(g, f.rec, f.n, f.r, f.force, f.block_energy, 0LL, 0, f.inv_dx, lds_all,
                                         sb - f.nsel, f.nk1);
-  if (a.trace && threadIdx.x == 0) a.trace[(size_t)sb * 8 + 7] = wall_clock64();
 }
 
 // The same pairing for fix edm_pair on a device-resident neighbour list: workgroups [0, nsel) run the selection over
@@ -2768,7 +2760,6 @@ __device__ __forceinline__ void limiter_stage(const HillList &h, const double *_
       // ordered tail -- so that seeing it is all the waiting workgroups have to do when there is no tail
       __builtin_amdgcn_s_waitcnt(0);
       if (threadIdx.x == 0) ready_publish(la.ready_flag, ready_word(la.ready_seq, EDM_READY_FINAL | err, k_first));
-      if (la.trace && threadIdx.x == 0) la.trace[(size_t)bid * 8 + 3] = wall_clock64();
     }
   } else if (concurrent && la.early_word && threadIdx.x >= NT - 64) {
     // the last wave, beside the limiter's wave and the two that copy: does the batch stay below the limit
@@ -2883,9 +2874,7 @@ __device__ __forceinline__ bool hill_integrals_body(const Geom &g, const Tables 
         __builtin_amdgcn_s_sleep(2);
         if (wall_clock64() - t0 > 1000000000ull) __builtin_trap();   // 10 s at 100 MHz: never, short of a lost workgroup
       }
-      if (la.trace && threadIdx.x == 0) la.trace[(size_t)bid * 8 + 2] = wall_clock64();
       limiter_stage<DIM, NT>(h, heights, h_const, added, la, bid, -1, s_val);
-      if (la.trace && threadIdx.x == 0) la.trace[(size_t)bid * 8 + 4] = wall_clock64();
       __syncthreads();
       return true;
     }
@@ -2893,8 +2882,6 @@ __device__ __forceinline__ bool hill_integrals_body(const Geom &g, const Tables 
   if (TPH != 64 && la.enabled && (tagged ? bid > (unsigned)nh_eff : bid >= ticket_blocks)) return false;
   TermConst<DIM> tc;
   term_const<DIM>(g, tc);
-  unsigned long long *wtrace = (TPH != 64 && la.enabled && la.trace) ? la.trace + (size_t)bid * 8 : nullptr;
-  if (wtrace && threadIdx.x == 0) wtrace[5] = wall_clock64();
   const double acc_part = hill_stencil_partial<DIM, TPH, PERB>(g, t, tc, c_r, hx_r, ht_r, height_r, live, lt);
   double acc = acc_part;
   acc = wave_sum(acc);
@@ -2910,16 +2897,10 @@ __device__ __forceinline__ bool hill_integrals_body(const Geom &g, const Tables 
       else if (la.enabled) publish(&added[hill], r);
       else added[hill] = r;
     }
-    if (tagged) {
-      if (la.trace && threadIdx.x == 0) la.trace[(size_t)bid * 8 + 1] = wall_clock64();
-      return false;
-    }
+    if (tagged) return false;
     if (la.enabled) {
-      if (la.trace && threadIdx.x == 0) la.trace[(size_t)bid * 8 + 1] = wall_clock64();
       if (!last_block_done(la.ticket, ticket_blocks, bid, ticket_blocks <= 512)) return false;
-      if (la.trace && threadIdx.x == 0) la.trace[(size_t)bid * 8 + 2] = wall_clock64();
       limiter_stage<DIM, NT>(h, heights, h_const, added, la, bid, -1);
-      if (la.trace && threadIdx.x == 0) la.trace[(size_t)bid * 8 + 4] = wall_clock64();
       __syncthreads();
       return true;
     }
@@ -2941,9 +2922,7 @@ __global__ void __launch_bounds__((TPH > BLOCK) ? TPH : BLOCK) k_hill_integrals(
     mark_tiles_body<DIM>(g, h, mk.flags, mk.list, mk.ntiles, mk.parity, (long long)(blockIdx.x - nb_int) * NT + threadIdx.x);
     return;
   }
-  if (la.trace && threadIdx.x == 0) la.trace[(size_t)blockIdx.x * 8] = wall_clock64();
   (void)hill_integrals_body<DIM, TPH, PERB>(g, t, h, heights, h_const, added, la, blockIdx.x, nb_int);
-  if (la.trace && threadIdx.x == 0) la.trace[(size_t)blockIdx.x * 8 + 7] = wall_clock64();
 }
 
 bool hill_integrals_can_chain_limit(long long nh) { return nh > 0 && nh <= 2048; }
@@ -3176,8 +3155,7 @@ __device__ __forceinline__ void hill_gather_body(const Geom &g, const Tables &t,
                                                  const HillList &h, const HillHeights &hh, const GatherPlan &plan,
                                                  int use_list, int *__restrict__ dirty_flag, int coherent,
                                                  long long tile, const unsigned long long *ready_flag = nullptr,
-                                                 unsigned long long ready_seq = 0, unsigned long long *trace = nullptr,
-                                                 int *s_dirty = nullptr) {
+                                                 unsigned long long ready_seq = 0, int *s_dirty = nullptr) {
   static_assert(!DEFER || (DIM == 1 && MODE == 0), "deferred heights: the 1-D in-place gather only");
   constexpr int R = (DIM == 1) ? 2 : 4;
   constexpr int NODES = BLOCK / PARTS;
@@ -3435,11 +3413,9 @@ __device__ __forceinline__ void hill_gather_body(const Geom &g, const Tables &t,
         }
       }
       // 2. the limiter's word (its workgroups were dispatched ahead of this one and wait for nobody)
-      if (trace && threadIdx.x == 0) trace[1] = wall_clock64();
       __shared__ unsigned long long s_word;
       if (threadIdx.x == 0) s_word = wait_for_word(ready_flag, ready_seq, false);
       __syncthreads();
-      if (trace && threadIdx.x == 0) trace[2] = wall_clock64();
       waited = true;
       const unsigned long long word = s_word;
       const int state = ready_state_of(word);
@@ -3746,18 +3722,15 @@ __global__ void __launch_bounds__(BLOCK) k_integrals_gather(Geom g, Tables t, do
   // (628 integrals workgroups for ~125 hills) and the tiles -- whose terms are the longest stretch of the launch --
   // then start 2-4 us late, behind hundreds of workgroups that exit at once.  When the tiles cannot fill the machine
   // (host-checked against two resident workgroups per CU) they go first.
-  // (`wg`: this workgroup's index in the order integrals | tiles, which the stamps and the rest of the code use)
+  // (`wg`: this workgroup's index in the order integrals | tiles, which the rest of the code uses)
   const unsigned ntile_all = gridDim.x - nb_emit - nb_int;
   const unsigned wg = tiles_first ? (bidx < ntile_all ? nb_int + bidx : bidx - ntile_all) : bidx;
-#define EDM_STAMP(k) do { if (la.trace && threadIdx.x == 0) la.trace[(size_t)wg * 8 + (k)] = wall_clock64(); } while (0)
-  EDM_STAMP(0);
   if (wg < nb_int) {
     const bool ran_limiter = hill_integrals_body<1, BLOCK, PERB>(g, t, h, heights, h_const, added, la, wg, nb_int);
     // the CV histogram needs the limiter's flags and the hills' positions, nothing of the gather: the limiter's
     // workgroup updates it while the gather applies heights (edm_bias.cpp:601-610)
     if (ran_limiter && post.enabled && !la.res->error)
       hist_batch<1>(post.hg, post.hist, h.nh, h.hx0, la.res, post.flags, post.flush_mode, threadIdx.x, BLOCK);
-    EDM_STAMP(7);
     return;
   }
   const unsigned tile = wg - nb_int, ntile = ntile_all;
@@ -3767,12 +3740,10 @@ __global__ void __launch_bounds__(BLOCK) k_integrals_gather(Geom g, Tables t, do
   const bool ticket_dirty = post.enabled && post.skip_hist && !post.rb_dst && ntile < 0xFFFFu;
   if (threadIdx.x == 0) s_dirty = 0;
   hill_gather_body<1, 0, 8, PERB, true>(g, t, rec, h, hh, plan, 0, dirty_flag, post.enabled, tile, la.ready_flag, la.ready_seq,
-                                        la.trace ? la.trace + (size_t)wg * 8 : nullptr, ticket_dirty ? &s_dirty : nullptr);
-  EDM_STAMP(6);
+                                        ticket_dirty ? &s_dirty : nullptr);
   if (!post.enabled) return;
   if (ticket_dirty) {
     tile_ticket_duplicate<PERB>(g, rec, post, ntile, tile, &s_dirty, &s_last);
-    EDM_STAMP(7);
     return;
   }
   // (the bookkeeping reads the limiter's result: a workgroup whose tile met no hill has not waited for it yet)
@@ -3780,8 +3751,6 @@ __global__ void __launch_bounds__(BLOCK) k_integrals_gather(Geom g, Tables t, do
   if (threadIdx.x == 0) (void)wait_for_word(la.ready_flag, la.ready_seq);
   __syncthreads();
   gather_post<1, PERB>(g, rec, h, hh, dirty_flag, post, ntile, tile);
-  EDM_STAMP(7);
-#undef EDM_STAMP
 }
 
 // rec[p] += partial[0][p] + partial[1][p] + ... in group (= hill list) order
@@ -4987,15 +4956,12 @@ __global__ void __launch_bounds__(BLOCK) k_ordered_records(Geom g, Tables t, Ord
   const bool in_grid = n < g.n[0];
   const int t1 = (t0 + ORD_NODES - 1 < g.n[0] - 1) ? t0 + ORD_NODES - 1 : g.n[0] - 1;
   const int p[1] = {in_grid ? n : 0};
-  unsigned long long *tr = a.trace ? a.trace + (size_t)blockIdx.x * 8 : nullptr;
-  if (tr && threadIdx.x == 0) tr[0] = wall_clock64();
   NodeTerms<1> nt;
   nt.inside = true;
   if (!a.terms) node_terms<1, PERB>(g, t, p, nt);   // (with the terms stored by the batch's launch the node side is not needed)
   const bool active = in_grid && nt.inside;   // (hills skip nodes outside a wall, gaussian_grid.h:273)
   TermConst<1> tc;
   term_const<1>(g, tc);
-  if (tr && threadIdx.x == 0) tr[1] = wall_clock64();
   double acc0 = 0, acc1 = 0;
   if (in_grid && part == 0 && !a.wait_flag) {   // (beside the hill batch: the grid's step-start copy is read behind the wait below)
     const double2 r0 = reinterpret_cast<const double2 *>(a.rec0)[n];
@@ -5101,9 +5067,7 @@ __global__ void __launch_bounds__(BLOCK) k_ordered_records(Geom g, Tables t, Ord
       if (threadIdx.x == 0) s_cnt = s_wcnt[0] + s_wcnt[1];
     }
     __syncthreads();
-    if (tr && threadIdx.x == 0 && base == 0) tr[2] = wall_clock64();
     const int nl = s_cnt;
-    if (tr && threadIdx.x == 0 && base == 0) tr[7] = (unsigned long long)nl;
     // (one listed hill per thread and trip: four of them unrolled side by side were tried -- the terms' branches keep
     //  the chains from interleaving, and with ~6 listed hills per chunk the parts beyond the first two sat idle: slower)
     if (a.terms) {
@@ -5142,7 +5106,6 @@ __global__ void __launch_bounds__(BLOCK) k_ordered_records(Geom g, Tables t, Ord
       }
     }
     __syncthreads();
-    if (tr && threadIdx.x == 0 && base == 0) tr[3] = wall_clock64();
     if (part == 0) {
       // (four listed hills per trip: their LDS reads are requested together and the products h * term computed off the
       //  chain; the adds -- rec += h1 term, then += h2 term where the limiter added an undo hill (a branch the whole
@@ -5178,7 +5141,6 @@ __global__ void __launch_bounds__(BLOCK) k_ordered_records(Geom g, Tables t, Ord
       }
     }
     __syncthreads();
-    if (tr && threadIdx.x == 0 && base == 0) tr[4] = wall_clock64();
     for (int e = part; e < nl; e += ORD_PARTS) {
       double2 out;
       out.x = s_v[e][tnode];
@@ -5187,9 +5149,7 @@ __global__ void __launch_bounds__(BLOCK) k_ordered_records(Geom g, Tables t, Ord
     }
     listed += nl;
     __syncthreads();
-    if (tr && threadIdx.x == 0 && base == 0) tr[5] = wall_clock64();
   }
-  if (tr && threadIdx.x == 0) tr[6] = wall_clock64();
 }
 
 // One wave that waits for the limiter's word of a batch and then for every emitter's flag: queued ahead of a record pass
@@ -5476,8 +5436,6 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_ordered(Geom g, OrderedFo
   // (the record pass ahead of this launch left without its records -- its gate gave up, see k_wait_word: leave too, without
   //  a partial sum: the host's poll runs out, and it queues both passes again)
   if (a.wait_flag && *a.status == 2) return;
-  unsigned long long *tr = a.trace ? a.trace + (size_t)blockIdx.x * 8 : nullptr;   // (development aid: EDM_HIP_TRACE=k1o)
-  if (tr && threadIdx.x == 0) tr[0] = wall_clock64();
   // ---- prologue: everything it reads from memory leaves at once (the hills' sample indices and correction flags, the
   //      run's first and last sample index, the first pair), two barriers ----
   long long i = beg + threadIdx.x;
@@ -5521,7 +5479,6 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_ordered(Geom g, OrderedFo
     oc.fast = g.interp && !g.periodic[0] && !g.bper[0];
     oc.inv_dx = 1.0 / g.dx[0];
   }
-  if (tr && threadIdx.x == 0) tr[1] = wall_clock64();
   double e_acc = 0;
   int row0 = 0, row1 = 0, nrows = 0;
   if (beg < end) {
@@ -5533,7 +5490,6 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_ordered(Geom g, OrderedFo
   }
   __syncthreads();
   oc.first_dirty = s_fd;
-  if (tr && threadIdx.x == 0) tr[2] = wall_clock64();
   const bool lean = oc.fast && nrows == row1 - row0 + 1 &&
                     (long long)oc.ntiles * a.nh_cap * ORD_NODES < (1ll << 31);   // (32-bit record offsets)
   OrderedLean L;
@@ -5594,7 +5550,6 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_ordered(Geom g, OrderedFo
         e_acc += v1;
         a.force[i1] = 0.0 - d1;
       }
-      if (tr && threadIdx.x == 0 && i < beg + BLOCK) tr[3] = wall_clock64();   // (first trip done)
     }
   } else {
     for (; i < end; i += BLOCK) {
@@ -5613,7 +5568,6 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_ordered(Geom g, OrderedFo
       a.force[i] = 0.0 - d;
     }
   }
-  if (tr && threadIdx.x == 0) tr[4] = wall_clock64();
   const double sum = block_sum(e_acc, red);
   if (threadIdx.x == 0) {
     if (tag) store_partial_tagged(block_energy, blockIdx.x, sum, tag);
