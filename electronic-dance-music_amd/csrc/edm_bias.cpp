@@ -1362,6 +1362,53 @@ static int do_post_add_hill(edm_hip_bias *b) {
   return EDM_HIP_OK;
 }
 
+// how every step entry opens: *energy zeroed, and the bias has to exist (or the rank be out of bounds)
+static int step_check(edm_hip_bias *b, const char *what, double *energy) {
+  if (energy) *energy = 0;
+  if (b->bias || b->b_outofbounds) return EDM_HIP_OK;
+  set_error(std::string(what) + " before subdivide");
+  return EDM_HIP_ERR_STATE;
+}
+
+// How a pair step opens: the checks, the counts clamped, and pre_add_hill first, as fix_edm_pair does (:174) -- a
+// pending overflow flush is part of the bias the forces see.  Out of bounds the n forces are zeroed (`host`: the array
+// lives in host memory) and the step is closed.  Returns STEP_GO_ON, or the step's result.
+static const int STEP_GO_ON = -1;
+static int pair_step_open(edm_hip_bias *b, long long &n, long long &n_samples, long long est_hill_count, double *force,
+                          bool host, double *energy) {
+  int rc = step_check(b, "pair_step", energy);
+  if (rc) return rc;
+  if (b->dim != 1) {
+    set_error("pair_step: the pair-distance CV is 1-D (fix_edm_pair.cpp:52)");
+    return EDM_HIP_ERR_ARG;
+  }
+  if (n < 0) n = 0;
+  if (n_samples < 0) n_samples = 0;
+  rc = do_pre_add_hill(b, est_hill_count < 0 ? n_samples : est_hill_count);
+  if (rc) return rc;
+  if (!b->b_outofbounds) return STEP_GO_ON;
+  if (n > 0) {
+    if (host)
+      memset(force, 0, sizeof(double) * (size_t)n);
+    else
+      EDM_HIP_TRY(hipMemset(force, 0, sizeof(double) * (size_t)n));
+  }
+  return do_post_add_hill(b);
+}
+
+// synchronises its streams when it goes out of scope unless disarmed: whatever makes an entry return early, no copy may
+// still be reading or writing the caller's arrays when it does
+struct StreamGuard {
+  hipStream_t a, c;   // (c: none when NULL)
+  bool armed = true;
+  void disarm() { armed = false; }
+  ~StreamGuard() {
+    if (!armed) return;
+    (void)hipStreamSynchronize(a);
+    if (c) (void)hipStreamSynchronize(c);
+  }
+};
+
 extern "C" {
 
 int edm_hip_bias_add_hills(edm_hip_bias *b, long long n, const double *d_x, int x_stride, const double *d_runiform,
@@ -1377,11 +1424,8 @@ int edm_hip_bias_add_hills(edm_hip_bias *b, long long n, const double *d_x, int 
 
 int edm_hip_bias_step(edm_hip_bias *b, long long n, const double *d_x, int x_stride, double *d_f, int f_stride,
                       const double *d_runiform, int apply_mask, long long est_hill_count, double *energy) {
-  if (energy) *energy = 0;
-  if (!b->bias && !b->b_outofbounds) {
-    set_error("step before subdivide");
-    return EDM_HIP_ERR_STATE;
-  }
+  int rc = step_check(b, "step", energy);
+  if (rc) return rc;
   int nblk = 0;
   unsigned long long ftag = 0;
   bool lookup_pending = false;
@@ -1412,7 +1456,7 @@ int edm_hip_bias_step(edm_hip_bias *b, long long n, const double *d_x, int x_str
       b->pending.on_launched_ctx = b->step_hook_ctx;
       lookup_pending = true;
     } else {
-      int rc = update_forces_enqueue(b->bias, n, d_x, x_stride, d_f, f_stride, b->d_mask, apply_mask, &nblk, ftag);
+      rc = update_forces_enqueue(b->bias, n, d_x, x_stride, d_f, f_stride, b->d_mask, apply_mask, &nblk, ftag);
       if (rc) return rc;
       if (n > 0 && b->step_hook) b->step_hook(b->step_hook_ctx);
     }
@@ -1423,7 +1467,7 @@ int edm_hip_bias_step(edm_hip_bias *b, long long n, const double *d_x, int x_str
   //  edm_bias.cpp:534-535, must not fall back to a stream wait for that: 20-30 us of idle GPU per step on W4)
   if (b->bias) b->bias->wait_polled = false;
   b->flush_forces = lookup_pending ? &b->pending : nullptr;
-  int rc = do_pre_add_hill(b, est_hill_count < 0 ? n : est_hill_count);
+  rc = do_pre_add_hill(b, est_hill_count < 0 ? n : est_hill_count);
   b->flush_forces = nullptr;
   if (rc) {
     if (lookup_pending) (void)pending_forces_flush(b->bias, &b->pending);
@@ -1441,15 +1485,8 @@ int edm_hip_bias_step(edm_hip_bias *b, long long n, const double *d_x, int x_str
     }
     if (flush_polled) b->bias->wait_polled = true;   // (whatever the new hills did: the forces were seen complete)
     if (rc) return rc;
-    double e = 0;
-    if (ftag && !b->bias->wait_polled && poll_tagged_partials(b->bias, nblk, ftag, &e)) {
-      b->bias->polled_forces++;
-    } else {
-      if (!b->bias->wait_polled) EDM_HIP_TRY(hipStreamSynchronize(b->bias->stream));
-      e = 0;
-      for (int k = 0; k < nblk; k++) e += b->bias->h_partials[ftag ? 2 * k : k];
-    }
-    if (energy) *energy = e;
+    rc = force_energy(b->bias, nblk, ftag, b->bias->wait_polled, energy);
+    if (rc) return rc;
   }
   return do_post_add_hill(b);
 }
@@ -1457,23 +1494,8 @@ int edm_hip_bias_step(edm_hip_bias *b, long long n, const double *d_x, int x_str
 int edm_hip_bias_pair_step(edm_hip_bias *b, long long n, const double *d_r, double *d_force, long long n_samples,
                            const double *d_sample_r, const double *d_runiform, long long est_hill_count,
                            double *energy) {
-  if (energy) *energy = 0;
-  if (!b->bias && !b->b_outofbounds) {
-    set_error("pair_step before subdivide");
-    return EDM_HIP_ERR_STATE;
-  }
-  if (b->dim != 1) {
-    set_error("pair_step: the pair-distance CV is 1-D (fix_edm_pair.cpp:52)");
-    return EDM_HIP_ERR_ARG;
-  }
-  // pre_add_hill first, as fix_edm_pair does (:174): a pending overflow flush is part of the bias the
-  // forces see
-  int rc = do_pre_add_hill(b, est_hill_count < 0 ? n_samples : est_hill_count);
-  if (rc) return rc;
-  if (b->b_outofbounds) {
-    if (n > 0) EDM_HIP_TRY(hipMemset(d_force, 0, sizeof(double) * (size_t)n));
-    return do_post_add_hill(b);
-  }
+  int rc = pair_step_open(b, n, n_samples, est_hill_count, d_force, false, energy);
+  if (rc != STEP_GO_ON) return rc;
   // forces (queued, not waited for), then the new hills behind them on the same stream: one host wait
   // (where the step's selection runs as a chained launch, the force kernel rides in that launch)
   b->pending = PendingForces();
@@ -1492,19 +1514,12 @@ int edm_hip_bias_pair_step(edm_hip_bias *b, long long n, const double *d_r, doub
   int rcf = pending_forces_flush(b->bias, &b->pending);
   if (rc) return rc;
   if (rcf) return rcf;
-  double e = 0;
-  if (tag && b->pending.tagged && poll_tagged_partials(b->bias, b->pending.nblk, tag, &e)) {
-    b->bias->polled_forces++;
-  } else {
-    // (a polled hill batch has shown the stream's last kernel past its read-back: the force kernel, earlier on the
-    //  stream, is complete and its partial sums are in host memory)
-    if ((tag && b->pending.tagged) || !b->bias->wait_polled) EDM_HIP_TRY(hipStreamSynchronize(b->bias->stream));
-    e = 0;
-    for (int k = 0; k < b->pending.nblk; k++) e += b->bias->h_partials[(tag && b->pending.tagged) ? 2 * k : k];
-  }
-  if (energy) *energy = e;
-  rc = do_post_add_hill(b);
-  return rc;
+  if (!b->pending.tagged) tag = 0;
+  // (untagged: a polled hill batch has shown the stream's last kernel past its read-back -- the force kernel, earlier on
+  //  the stream, is complete and its partial sums are in host memory)
+  rc = force_energy(b->bias, b->pending.nblk, tag, !tag && b->bias->wait_polled, energy);
+  if (rc) return rc;
+  return do_post_add_hill(b);
 }
 
 // fix edm_pair's hill step in the REFERENCE'S order (lammps/fix_edm_pair.cpp:173-247): the step's hills are applied as
@@ -1649,11 +1664,71 @@ static int ordered_step_redo_after_gate(edm_hip_bias *b, int *nblk) {
   return EDM_HIP_OK;
 }
 
+// force_energy's wait in a reference-order step: the second stream, then the object's; passes on the second stream that
+// gave up at their gate run again behind the batch, and the energy is theirs
+static int ordered_step_wait(void *ctx, int *nblk) {
+  edm_hip_bias *b = static_cast<edm_hip_bias *>(ctx);
+  if (b->ord_on_own_stream) EDM_HIP_TRY(hipStreamSynchronize(b->ord_stream));
+  EDM_HIP_TRY(hipStreamSynchronize(b->bias->stream));
+  if (b->ord_on_own_stream && *reinterpret_cast<volatile int *>(b->h_ord_status) == 2) {
+    int rc = ordered_step_redo_after_gate(b, nblk);
+    if (rc) return rc;
+    EDM_HIP_TRY(hipStreamSynchronize(b->bias->stream));
+  }
+  return EDM_HIP_OK;
+}
+
+// The end of a reference-order step behind its hill path (`rc`: that path's result).  The force pass over b->ord_early's
+// pairs -- the pair array, or the pair list -- went out from inside the hill batch, goes out now behind the batch's
+// records, or, without a new hill, goes out plainly; then its energy.
+static int ordered_step_finish(edm_hip_bias *b, int rc, double *energy) {
+  edm_hip_gauss *g = b->bias;
+  edm_hip_bias::OrderedEarly &oe = b->ord_early;
+  if (rc) {
+    if (b->ord_on_own_stream) (void)hipStreamSynchronize(b->ord_stream);
+    return rc;
+  }
+  int nblk = 0;
+  unsigned long long tag = 0;   // (of the pass whose sums are read; a redone step has taken a fresh one)
+  if (oe.done) {
+    // (the batch's deferred log lines -- positions and per-hill bias from the read-back region -- are picked up NOW, while
+    //  the record and force pass run: at the start of the next cycle, where they would be fetched otherwise, they sit in
+    //  front of its first launch, ~2 us)
+    rc = resolve_deferred_log(b);
+    if (rc) return rc;
+    // (the force pass went out behind the hill batch, before the host had the limiter's result)
+    if (oe.rc) return oe.rc;
+    nblk = oe.nblk;
+    tag = oe.tag;
+  } else if ((oe.list || oe.n > 0) && b->last_batch.valid && b->last_batch.nh > 0) {
+    rc = ordered_forces_enqueue(b);
+    if (rc) return rc;
+    nblk = oe.nblk;
+    tag = oe.tag;
+  } else if (oe.list) {
+    // no new hill this step (none accepted, or edm_bias.cpp:534-535 skipped them): every pair sees the same bias
+    PairListArgs pl = oe.pl;
+    pl.partial_tag = oe.tag;
+    EDM_HIP_TRY(launch_pairlist_forces(g->g, g->rec, pl, g->d_partials, g->stream, &nblk));
+    tag = oe.tag;
+  } else if (oe.n > 0) {
+    b->pending.active = true;
+    b->pending.n = oe.n;
+    b->pending.d_r = oe.d_r;
+    b->pending.d_force = oe.d_force;
+    b->pending.tag = oe.tag;
+    rc = pending_forces_flush(g, &b->pending);
+    if (rc) return rc;
+    nblk = b->pending.nblk;
+    tag = b->pending.tagged ? oe.tag : 0;
+  }
+  return force_energy(g, nblk, tag, false, energy, ordered_step_wait, b);
+}
+
 static int pair_step_ordered_device(edm_hip_bias *b, long long n, const double *d_r, double *d_force,
                                     const int *d_first_sample, long long n_samples, const double *d_sample_r,
                                     const double *d_runiform, double *energy) {
   edm_hip_gauss *g = b->bias;
-  hipStream_t s = g->stream;
   int rc = ordered_snapshot(b);
   if (rc) return rc;
   b->pending = PendingForces();
@@ -1670,84 +1745,17 @@ static int pair_step_ordered_device(edm_hip_bias *b, long long n, const double *
   b->ord_early.armed = false;
   b->ord_step_active = false;
   b->ord_snap_pending = false;   // (no hill batch was applied: nobody needs the copy)
-  if (rc) {
-    if (b->ord_on_own_stream) (void)hipStreamSynchronize(b->ord_stream);
-    return rc;
-  }
-  int nblk = 0;
-  bool tagged = false;
-  const unsigned long long tag = b->ord_early.tag;   // (a redone step has taken a fresh one)
-  if (b->ord_early.done) {
-    // (the batch's deferred log lines -- positions and per-hill bias from the read-back region -- are picked up NOW, while
-    //  the record and force pass run: at the start of the next cycle, where they would be fetched otherwise, they sit in
-    //  front of its first launch, ~2 us)
-    rc = resolve_deferred_log(b);
-    if (rc) return rc;
-  }
-  if (b->ord_early.done) {
-    // (the force pass went out behind the hill batch, before the host had the limiter's result)
-    if (b->ord_early.rc) return b->ord_early.rc;
-    nblk = b->ord_early.nblk;
-    tagged = tag != 0;
-  } else if (n > 0 && b->last_batch.valid && b->last_batch.nh > 0) {
-    rc = ordered_forces_enqueue(b);
-    if (rc) return rc;
-    nblk = b->ord_early.nblk;
-    tagged = tag != 0;
-  } else if (n > 0) {
-    // no new hill this step (none accepted, or edm_bias.cpp:534-535 skipped them): every pair sees the same bias
-    b->pending.active = true;
-    b->pending.n = n;
-    b->pending.d_r = d_r;
-    b->pending.d_force = d_force;
-    b->pending.tag = tag;
-    rc = pending_forces_flush(g, &b->pending);
-    if (rc) return rc;
-    nblk = b->pending.nblk;
-    tagged = tag && b->pending.tagged;
-  }
-  double e = 0;
-  if (!(tagged && poll_tagged_partials(g, nblk, tag, &e))) {
-    if (b->ord_on_own_stream) EDM_HIP_TRY(hipStreamSynchronize(b->ord_stream));
-    EDM_HIP_TRY(hipStreamSynchronize(s));
-    if (b->ord_on_own_stream && *reinterpret_cast<volatile int *>(b->h_ord_status) == 2) {
-      rc = ordered_step_redo_after_gate(b, &nblk);
-      if (rc) return rc;
-      EDM_HIP_TRY(hipStreamSynchronize(s));
-    }
-    e = 0;
-    for (int k = 0; k < nblk; k++) e += g->h_partials[tagged ? 2 * k : k];
-  } else {
-    g->polled_forces++;
-  }
-  if (energy) *energy = e;
-  return EDM_HIP_OK;
+  return ordered_step_finish(b, rc, energy);
 }
 
 int edm_hip_bias_pair_step_ordered(edm_hip_bias *b, long long n, const double *d_r, double *d_force,
                                    const int *d_first_sample, long long n_samples, const double *d_sample_r,
                                    const double *d_runiform, long long est_hill_count, double *energy) {
-  if (energy) *energy = 0;
-  if (!b->bias && !b->b_outofbounds) {
-    set_error("pair_step before subdivide");
-    return EDM_HIP_ERR_STATE;
-  }
-  if (b->dim != 1) {
-    set_error("pair_step: the pair-distance CV is 1-D (fix_edm_pair.cpp:52)");
-    return EDM_HIP_ERR_ARG;
-  }
-  if (n < 0) n = 0;
-  if (n_samples < 0) n_samples = 0;
-  int rc = do_pre_add_hill(b, est_hill_count < 0 ? n_samples : est_hill_count);
-  if (rc) return rc;
-  if (b->b_outofbounds) {
-    if (n > 0) EDM_HIP_TRY(hipMemset(d_force, 0, sizeof(double) * (size_t)n));
-    return do_post_add_hill(b);
-  }
+  int rc = pair_step_open(b, n, n_samples, est_hill_count, d_force, false, energy);
+  if (rc != STEP_GO_ON) return rc;
   rc = pair_step_ordered_device(b, n, d_r, d_force, d_first_sample, n_samples, d_sample_r, d_runiform, energy);
   if (rc) return rc;
-  rc = do_post_add_hill(b);
-  return rc;
+  return do_post_add_hill(b);
 }
 
 // ... for a caller whose arrays live in HOST memory (the host-list fix edm_pair): copies queued on the object's stream
@@ -1755,34 +1763,15 @@ int edm_hip_bias_pair_step_ordered(edm_hip_bias *b, long long n, const double *d
 int edm_hip_bias_pair_step_ordered_host(edm_hip_bias *b, long long n, const double *h_r, double *h_force,
                                         const int *h_first_sample, long long n_samples, const double *h_sample_r,
                                         const double *h_runiform, long long est_hill_count, double *energy) {
-  if (energy) *energy = 0;
-  if (!b->bias && !b->b_outofbounds) {
-    set_error("pair_step before subdivide");
-    return EDM_HIP_ERR_STATE;
-  }
-  if (b->dim != 1) {
-    set_error("pair_step: the pair-distance CV is 1-D (fix_edm_pair.cpp:52)");
-    return EDM_HIP_ERR_ARG;
-  }
-  if (n < 0) n = 0;
-  if (n_samples < 0) n_samples = 0;
-  int rc = do_pre_add_hill(b, est_hill_count < 0 ? n_samples : est_hill_count);
-  if (rc) return rc;
-  if (b->b_outofbounds) {
-    if (n > 0) memset(h_force, 0, sizeof(double) * (size_t)n);
-    return do_post_add_hill(b);
-  }
+  int rc = pair_step_open(b, n, n_samples, est_hill_count, h_force, true, energy);
+  if (rc != STEP_GO_ON) return rc;
   hipStream_t s = b->bias->stream;
   EDM_HIP_TRY(b->hs_r.reserve((size_t)(n > 0 ? n : 1)));
   EDM_HIP_TRY(b->hs_f.reserve((size_t)(n > 0 ? n : 1)));
   EDM_HIP_TRY(b->hs_x.reserve((size_t)(n_samples > 0 ? n_samples : 1)));
   EDM_HIP_TRY(b->hs_u.reserve((size_t)(n_samples > 0 ? n_samples : 1)));
   EDM_HIP_TRY(b->ord_first.reserve((size_t)(n > 0 ? n : 1)));
-  // (whatever happens below, no copy may still be reading or writing the caller's arrays when the call returns)
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() { (void)hipStreamSynchronize(s); }
-  } guard{s};
+  StreamGuard guard{s, nullptr};   // (always armed: the call ends with a stream wait anyway)
   if (n > 0) {
     EDM_HIP_TRY(hipMemcpyAsync(b->hs_r.p, h_r, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     if (h_first_sample)
@@ -1813,23 +1802,8 @@ int edm_hip_bias_pair_step_ordered_host(edm_hip_bias *b, long long n, const doub
 int edm_hip_bias_pair_step_host(edm_hip_bias *b, long long n, const double *h_r, double *h_force, long long n_samples,
                                 const double *h_sample_r, const double *h_runiform, long long est_hill_count,
                                 double *energy) {
-  if (energy) *energy = 0;
-  if (!b->bias && !b->b_outofbounds) {
-    set_error("pair_step before subdivide");
-    return EDM_HIP_ERR_STATE;
-  }
-  if (b->dim != 1) {
-    set_error("pair_step: the pair-distance CV is 1-D (fix_edm_pair.cpp:52)");
-    return EDM_HIP_ERR_ARG;
-  }
-  if (n < 0) n = 0;
-  if (n_samples < 0) n_samples = 0;
-  int rc = do_pre_add_hill(b, est_hill_count < 0 ? n_samples : est_hill_count);
-  if (rc) return rc;
-  if (b->b_outofbounds) {
-    if (n > 0) memset(h_force, 0, sizeof(double) * (size_t)n);
-    return do_post_add_hill(b);
-  }
+  int rc = pair_step_open(b, n, n_samples, est_hill_count, h_force, true, energy);
+  if (rc != STEP_GO_ON) return rc;
   hipStream_t s = b->bias->stream;
   if (!b->copy_stream) {
     EDM_HIP_TRY(hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking));
@@ -1841,15 +1815,7 @@ int edm_hip_bias_pair_step_host(edm_hip_bias *b, long long n, const double *h_r,
   EDM_HIP_TRY(b->hs_u.reserve((size_t)(n_samples > 0 ? n_samples : 1)));
   int nblk = 0;
   b->bias->wait_polled = false;
-  // (whatever happens below -- a full overflow buffer, a communicator error -- no copy may still be reading or writing
-  //  the caller's arrays when the call returns)
-  struct CopyGuard {
-    hipStream_t a, c;
-    ~CopyGuard() {
-      (void)hipStreamSynchronize(a);
-      (void)hipStreamSynchronize(c);
-    }
-  } copy_guard{s, b->copy_stream};
+  StreamGuard guard{s, b->copy_stream};   // (a full overflow buffer, a communicator error, ...)
   if (n > 0) {
     EDM_HIP_TRY(hipMemcpyAsync(b->hs_r.p, h_r, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
     rc = pair_forces_enqueue(b->bias, n, b->hs_r.p, b->hs_f.p, &nblk);   // (behind the overflow flush, ahead of the new hills)
@@ -1870,10 +1836,9 @@ int edm_hip_bias_pair_step_host(edm_hip_bias *b, long long n, const double *h_r,
   b->pending = PendingForces();
   rc = process_new_hills(b, n_samples, d_samples, 1, h_runiform ? b->hs_u.p : nullptr, -1);
   if (rc) return rc;
-  if (!b->bias->wait_polled) EDM_HIP_TRY(hipStreamSynchronize(s));
+  rc = force_energy(b->bias, nblk, 0, b->bias->wait_polled, energy);
+  if (rc) return rc;
   if (n > 0) EDM_HIP_TRY(hipStreamSynchronize(b->copy_stream));
-  const double e = pair_forces_finish(b->bias, nblk);
-  if (energy) *energy = e;
   return do_post_add_hill(b);
 }
 
@@ -1934,11 +1899,8 @@ static void delta_copy_queue(void *ctx) {
 int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int x_stride, double *h_f, int f_stride,
                            const int *h_mask, const double *h_runiform, int apply_mask, int hill_step,
                            long long est_hill_count, double *energy) {
-  if (energy) *energy = 0;
-  if (!b->bias && !b->b_outofbounds) {
-    set_error("step before subdivide");
-    return EDM_HIP_ERR_STATE;
-  }
+  int rc = step_check(b, "step", energy);
+  if (rc) return rc;
   if (n < 0) n = 0;
   const int dim = (int)b->dim;
   if (n > 0 && (x_stride < dim || f_stride < dim)) {
@@ -1951,7 +1913,7 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
   }
   if (b->b_outofbounds) {
     if (!hill_step) return EDM_HIP_OK;
-    int rc = do_pre_add_hill(b, est_hill_count < 0 ? n : est_hill_count);
+    rc = do_pre_add_hill(b, est_hill_count < 0 ? n : est_hill_count);
     return rc ? rc : do_post_add_hill(b);
   }
   hipStream_t s = b->bias->stream;
@@ -1974,16 +1936,7 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
   PIECES = PIECES < 1 ? 1 : (PIECES > MAX_PIECES ? MAX_PIECES : PIECES);
   if (!b->delta_ev[0])
     for (int c = 0; c < MAX_PIECES; c++) EDM_HIP_TRY(hipEventCreateWithFlags(&b->delta_ev[c], hipEventDisableTiming));
-  // (whatever happens below, no copy may still be reading or writing the caller's arrays when the call returns)
-  struct StreamGuard {
-    hipStream_t a, c;
-    bool armed;
-    ~StreamGuard() {
-      if (!armed) return;
-      (void)hipStreamSynchronize(a);
-      (void)hipStreamSynchronize(c);
-    }
-  } guard{s, b->copy_stream, true};
+  StreamGuard guard{s, b->copy_stream};
   if (n > 0) {
     // (whole rows: a copy of the caller's own that spans the block must not straddle locked and unlocked memory)
     host_block_register(b, edm_hip_bias::REG_X, h_x, sizeof(double) * (size_t)n * (size_t)x_stride);
@@ -2003,7 +1956,6 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
   const int *saved_mask = b->d_mask;
   if (apply_mask >= 0) b->d_mask = b->hs_mask.p;
   DeltaCopy dc{b, n, dim, PIECES, 0, false};
-  int rc;
   if (hill_step) {
     b->step_hook = delta_copy_queue;
     b->step_hook_ctx = &dc;
@@ -2042,7 +1994,7 @@ int edm_hip_bias_step_host(edm_hip_bias *b, long long n, const double *h_x, int 
   }
   // (success: the step's completion record is behind the uploads on the main stream, every piece's event has been
   //  waited for on the copy stream -- nothing of the caller's is in flight, no stream wait needed: ~17 us each)
-  guard.armed = false;
+  guard.disarm();
   return EDM_HIP_OK;
 }
 
@@ -2106,12 +2058,9 @@ int edm_hip_bias_pair_list_upload(edm_hip_bias *b, long long npairs, const int *
 
 int edm_hip_bias_pair_list_step(edm_hip_bias *b, int nlocal, int itype, int jtype, const double *d_x, double *d_fdelta,
                                 int hill_step, long long est_hill_count, double *energy, long long *ncalls) {
-  if (energy) *energy = 0;
   if (ncalls) *ncalls = 0;
-  if (!b->bias && !b->b_outofbounds) {
-    set_error("pair_list_step before subdivide");
-    return EDM_HIP_ERR_STATE;
-  }
+  int rc = step_check(b, "pair_list_step", energy);
+  if (rc) return rc;
   if (b->pl_npairs < 0) {
     set_error("pair_list_step before pair_list_upload");
     return EDM_HIP_ERR_STATE;
@@ -2125,7 +2074,6 @@ int edm_hip_bias_pair_list_step(edm_hip_bias *b, int nlocal, int itype, int jtyp
     return EDM_HIP_ERR_STATE;
   }
   const long long npairs = b->pl_npairs, nall = b->pl_nall;
-  int rc = EDM_HIP_OK;
   if (hill_step) {
     rc = do_pre_add_hill(b, est_hill_count);   // overflow flush before any force (fix_edm_pair.cpp:174)
     if (rc) return rc;
@@ -2213,61 +2161,24 @@ int edm_hip_bias_pair_list_step(edm_hip_bias *b, int nlocal, int itype, int jtyp
     b->d_mask = saved_mask;
     b->pl_view_x = nullptr;
   }
-  // (a step without hills: the force pass goes alone, its workgroups tag their partial energy sums and the host looks at
-  //  the slots instead of waiting for the stream, see edm_hip_gauss_pair_forces)
-  unsigned long long tag = 0;
-  int nblk_ordered = 0;
   if (ordered) {
-    if (rc) {
-      if (b->ord_on_own_stream) (void)hipStreamSynchronize(b->ord_stream);
-      return rc;
-    }
-    tag = b->ord_early.tag;   // (a step redone after an exceeded launch bound has taken a fresh one)
-    a.partial_tag = tag;
-    if (b->ord_early.done) {
-      int rcl = resolve_deferred_log(b);   // (while the force pass runs, see pair_step_ordered_device)
-      if (rcl) return rcl;
-    }
-    if (b->ord_early.done) {
-      if (b->ord_early.rc) return b->ord_early.rc;
-      nblk_ordered = b->ord_early.nblk;
-    } else if (b->last_batch.valid && b->last_batch.nh > 0) {
-      b->ord_early.list = true;
-      b->ord_early.pl = a;
-      rc = ordered_forces_enqueue(b);
-      if (rc) return rc;
-      nblk_ordered = b->ord_early.nblk;
-    } else {   // (no new hill: every entry sees the same bias)
-      EDM_HIP_TRY(launch_pairlist_forces(b->bias->g, b->bias->rec, a, b->bias->d_partials, s, &nblk_ordered));
-    }
-  } else if (b->pending.active && forces_poll_enabled()) {   // (no hills this step, or the step's new hills were skipped)
-    tag = ++b->bias->force_seq;
-    b->pending.pl.partial_tag = tag;
-  }
-  int rcf = pending_forces_flush(b->bias, &b->pending);   // (no hill launch carried it: nothing has touched the grid)
-  if (rc) return rc;
-  if (rcf) return rcf;
-  int nblk = ordered ? nblk_ordered : b->pending.nblk;
-  int nblk_redo = -1;
-  double e = 0;
-  if (tag && poll_tagged_partials(b->bias, nblk, tag, &e)) {
-    b->bias->polled_forces++;
+    rc = ordered_step_finish(b, rc, energy);
+    if (rc) return rc;
   } else {
-    // (a polled hill batch has shown the stream past the force pass queued ahead of it)
-    if (ordered && b->ord_on_own_stream) EDM_HIP_TRY(hipStreamSynchronize(b->ord_stream));
-    if (tag || !b->bias->wait_polled) EDM_HIP_TRY(hipStreamSynchronize(s));
-    if (ordered && b->ord_on_own_stream && *reinterpret_cast<volatile int *>(b->h_ord_status) == 2) {
-      int nb2 = 0;
-      rc = ordered_step_redo_after_gate(b, &nb2);
-      if (rc) return rc;
-      EDM_HIP_TRY(hipStreamSynchronize(s));
-      nblk_redo = nb2;
+    // (a step without hills: the force pass goes alone, its workgroups tag their partial energy sums and the host looks
+    //  at the slots instead of waiting for the stream, see edm_hip_gauss_pair_forces)
+    unsigned long long tag = 0;
+    if (b->pending.active && forces_poll_enabled()) {   // (no hills this step, or the step's new hills were skipped)
+      tag = ++b->bias->force_seq;
+      b->pending.pl.partial_tag = tag;
     }
-    if (nblk_redo >= 0) nblk = nblk_redo;
-    e = 0;
-    for (int k = 0; k < nblk; k++) e += b->bias->h_partials[tag ? 2 * k : k];
+    int rcf = pending_forces_flush(b->bias, &b->pending);   // (no hill launch carried it: nothing has touched the grid)
+    if (rc) return rc;
+    if (rcf) return rcf;
+    // (untagged: a polled hill batch has shown the stream past the force pass queued ahead of it)
+    rc = force_energy(b->bias, b->pending.nblk, tag, !tag && b->bias->wait_polled, energy);
+    if (rc) return rc;
   }
-  if (energy) *energy = e;
   if (ncalls) *ncalls = hill_step ? b->pl_calls : 0;
   return hill_step ? do_post_add_hill(b) : EDM_HIP_OK;
 }

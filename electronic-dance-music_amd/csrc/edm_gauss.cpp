@@ -518,6 +518,22 @@ int edm_hip_grid_write(const edm_hip_grid *g, const char *filename) {
   return write_plumed(g->g, v.data(), g->g.has_deriv ? dv.data() : nullptr, filename);
 }
 
+// device coordinates, values and derivatives of a batch of points: temporaries of one call, freed when it returns
+struct PointBufs {
+  DevBuf<double> x, e, d;
+  hipError_t reserve(size_t n, int dim) {
+    hipError_t err = x.reserve(n * dim);
+    if (err == hipSuccess) err = e.reserve(n);
+    if (err == hipSuccess) err = d.reserve(n * dim);
+    return err;
+  }
+  ~PointBufs() {
+    x.release();
+    e.release();
+    d.release();
+  }
+};
+
 // Grid::add (grid.h:275-290): dst += scale * src(x_node) + offset, node by node, `src` evaluated through ITS
 // get_value_deriv (src_geom carries the gaussian boundary when src is a GaussGrid, plain_geom otherwise; a
 // source without derivative records answers with its nearest-lower node).  Chunked so that a 512^3 grid needs
@@ -526,24 +542,21 @@ static int grid_add_from(const Geom &dst, double *dst_base, hipStream_t s, doubl
                          const double *src_base, double scale, double offset) {
   const long long chunk = dst.total < (1ll << 22) ? dst.total : (1ll << 22);
   if (chunk <= 0) return EDM_HIP_OK;
-  double *dx = nullptr, *dE = nullptr, *dD = nullptr;
-  EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dx), sizeof(double) * (size_t)chunk * dst.dim));
-  EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dE), sizeof(double) * (size_t)chunk));
-  EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dD), sizeof(double) * (size_t)chunk * dst.dim));
+  PointBufs p;
+  EDM_HIP_TRY(p.reserve((size_t)chunk, dst.dim));
   for (long long first = 0; first < dst.total; first += chunk) {
     const long long cnt = (dst.total - first < chunk) ? dst.total - first : chunk;
-    EDM_HIP_TRY(launch_node_coords(dst, first, cnt, dx, s));
+    EDM_HIP_TRY(launch_node_coords(dst, first, cnt, p.x.p, s));
     if (src_geom.has_deriv) {
       LookupArgs a{};
-      a.n = cnt; a.x = dx; a.x_stride = dst.dim; a.energy = dE; a.f = dD; a.apply_mask = -1;
+      a.n = cnt; a.x = p.x.p; a.x_stride = dst.dim; a.energy = p.e.p; a.f = p.d.p; a.apply_mask = -1;
       EDM_HIP_TRY(launch_lookup(src_geom, src_base, LOOKUP_VALUES, a, scratch, nullptr, s));
     } else {
-      EDM_HIP_TRY(launch_nearest_values(src_geom, src_base, cnt, dx, dst.dim, dE, dD, s));
+      EDM_HIP_TRY(launch_nearest_values(src_geom, src_base, cnt, p.x.p, dst.dim, p.e.p, p.d.p, s));
     }
-    EDM_HIP_TRY(launch_axpy_nodes(dst, dst_base, first, cnt, dE, dD, scale, offset, s));
+    EDM_HIP_TRY(launch_axpy_nodes(dst, dst_base, first, cnt, p.e.p, p.d.p, scale, offset, s));
   }
   EDM_HIP_TRY(hipStreamSynchronize(s));
-  (void)hipFree(dx); (void)hipFree(dE); (void)hipFree(dD);
   return EDM_HIP_OK;
 }
 static int need_scratch(edm_hip_grid *g) {
@@ -571,6 +584,75 @@ int edm_hip_grid_add_gauss(edm_hip_grid *g, const edm_hip_gauss *other, double s
   return grid_add_from(g->g, g->values, g->stream, g->scratch, other->g, other->rec, scale, offset);
 }
 
+// The points a multi_write writes (grid.h:509-674): box_min + k*dx over the box, `counts` per dimension, filtered by
+// in_grid -- their coordinates (dim per point), their index in the box and their index along the first dimension
+struct BoxWalk {
+  unsigned int counts[3] = {1, 1, 1}, extra_n = 0;
+  std::vector<double> xs;
+  std::vector<size_t> which;
+  std::vector<unsigned int> sup0;
+  BoxWalk(const Geom &q, const double *box_min, const double *box_max, const int *b_periodic, int b_lammps_format) {
+    if (b_lammps_format) extra_n = (unsigned int)(box_min[0] / q.dx[0]);
+    size_t total = 1;
+    for (int d = 0; d < q.dim; d++) {
+      counts[d] = (unsigned int)(int)ceil((box_max[d] - box_min[d]) / q.dx[d]);
+      counts[d] = b_periodic[d] ? counts[d] : counts[d] + 1;
+      total *= counts[d];
+    }
+    xs.reserve(total * q.dim);
+    for (size_t i = 0; i < total; i++) {
+      size_t tmp = i, sup[3] = {0, 0, 0};
+      double x[3];
+      int d;
+      for (d = 0; d < q.dim - 1; d++) {
+        sup[d] = tmp % counts[d];
+        tmp = (tmp - sup[d]) / counts[d];
+        x[d] = sup[d] * q.dx[d] + box_min[d];
+      }
+      sup[d] = tmp;
+      x[d] = sup[d] * q.dx[d] + box_min[d];
+      bool in = true;
+      for (d = 0; d < q.dim; d++)
+        if (!q.periodic[d] && (x[d] < q.min[d] || x[d] >= q.max[d] - q.dx[d])) in = false;
+      if (!in) continue;
+      which.push_back(i);
+      sup0.push_back((unsigned int)sup[0]);
+      for (d = 0; d < q.dim; d++) xs.push_back(x[d]);
+    }
+  }
+  // the file: the PLUMED header or the LAMMPS table's preamble, then per point its LAMMPS index, coordinates, value
+  // and -- with `der` -- the negated derivative columns
+  int write(const Geom &q, const char *filename, const double *box_min, const double *box_max, const int *b_periodic,
+            int b_lammps_format, const std::vector<double> &val, const std::vector<double> *der) const {
+    FILE *fp = fopen(filename, "w");
+    if (!fp) {
+      set_error(std::string("cannot open ") + filename);
+      return EDM_HIP_ERR_IO;
+    }
+    if (!b_lammps_format) {
+      long long bins[3];
+      for (int d = 0; d < q.dim; d++) bins[d] = b_periodic[d] ? (long long)counts[d] : (long long)counts[d] - 1;
+      edm::put_header(fp, der ? 1 : 0, q.dim, bins, box_min, box_max, b_periodic);
+    } else {
+      fprintf(fp, "#Auto generated by electronic-dance-music\n\n");
+      fprintf(fp, "EDM\n");
+      fprintf(fp, "N %u R %g %g\n\n", extra_n + counts[0], q.dx[0], box_max[0]);
+      for (size_t i = 1; i < extra_n; i++) fprintf(fp, "%zu %g 0.0 0.0\n", i, i * q.dx[0]);
+    }
+    for (size_t j = 0; j < which.size(); j++) {
+      if (b_lammps_format) fprintf(fp, "%zu ", which[j] + extra_n);
+      for (int d = 0; d < q.dim; d++) fprintf(fp, "%.8f ", xs[j * q.dim + d]);
+      fprintf(fp, "%.8f ", val[j]);
+      if (der)
+        for (int d = 0; d < q.dim; d++) fprintf(fp, "%.8f ", -(*der)[j * q.dim + d]);
+      fprintf(fp, "\n");
+      if (sup0[j] == counts[0] - 1) fprintf(fp, "\n");
+    }
+    fclose(fp);
+    return EDM_HIP_OK;
+  }
+};
+
 static int multi_write_records(const Geom &q, const double *rec, hipStream_t s, double *scratch, const char *filename,
                                const double *box_min, const double *box_max, const int *b_periodic, int b_lammps_format);
 
@@ -590,61 +672,21 @@ int edm_hip_grid_multi_write(const edm_hip_grid *g, const char *filename, const 
   std::vector<double> v((size_t)q.total);
   int rc = edm_hip_grid_download(g, v.data());
   if (rc) return rc;
-  unsigned int counts[3] = {1, 1, 1}, extra_n = 0;
-  if (b_lammps_format) extra_n = (unsigned int)(box_min[0] / q.dx[0]);
-  size_t total = 1;
-  for (int d = 0; d < q.dim; d++) {
-    counts[d] = (unsigned int)(int)ceil((box_max[d] - box_min[d]) / q.dx[d]);
-    counts[d] = b_periodic[d] ? counts[d] : counts[d] + 1;
-    total *= counts[d];
-  }
-  FILE *fp = fopen(filename, "w");
-  if (!fp) {
-    set_error(std::string("cannot open ") + filename);
-    return EDM_HIP_ERR_IO;
-  }
-  if (!b_lammps_format) {
-    long long bins[3];
-    for (int d = 0; d < q.dim; d++) bins[d] = b_periodic[d] ? (long long)counts[d] : (long long)counts[d] - 1;
-    edm::put_header(fp, 0, q.dim, bins, box_min, box_max, b_periodic);
-  } else {
-    fprintf(fp, "#Auto generated by electronic-dance-music\n\n");
-    fprintf(fp, "EDM\n");
-    fprintf(fp, "N %u R %g %g\n\n", extra_n + counts[0], q.dx[0], box_max[0]);
-    for (size_t i = 1; i < extra_n; i++) fprintf(fp, "%zu %g 0.0 0.0\n", i, i * q.dx[0]);
-  }
-  for (size_t i = 0; i < total; i++) {
-    size_t tmp = i, sup[3] = {0, 0, 0};
-    double x[3];
-    int d;
-    for (d = 0; d < q.dim - 1; d++) {
-      sup[d] = tmp % counts[d];
-      tmp = (tmp - sup[d]) / counts[d];
-      x[d] = sup[d] * q.dx[d] + box_min[d];
-    }
-    sup[d] = tmp;
-    x[d] = sup[d] * q.dx[d] + box_min[d];
-    bool in = true;
-    for (d = 0; d < q.dim; d++)
-      if (!q.periodic[d] && (x[d] < q.min[d] || x[d] >= q.max[d] - q.dx[d])) in = false;
-    if (!in) continue;
+  const BoxWalk w(q, box_min, box_max, b_periodic, b_lammps_format);
+  std::vector<double> val(w.which.size());
+  for (size_t j = 0; j < val.size(); j++) {
     long long flat = 0, mul = 1;
-    for (d = 0; d < q.dim; d++) {
-      double w;
-      long long idx = node_index(q, d, x[d], &w);
+    for (int d = 0; d < q.dim; d++) {
+      double frac;
+      long long idx = node_index(q, d, w.xs[j * q.dim + d], &frac);
       if (idx < 0) idx = 0;
       if (idx > q.n[d] - 1) idx = q.n[d] - 1;
       flat += idx * mul;
       mul *= q.n[d];
     }
-    if (b_lammps_format) fprintf(fp, "%zu ", i + extra_n);
-    for (d = 0; d < q.dim; d++) fprintf(fp, "%.8f ", x[d]);
-    fprintf(fp, "%.8f ", v[(size_t)flat]);
-    fprintf(fp, "\n");
-    if (sup[0] == counts[0] - 1) fprintf(fp, "\n");
+    val[j] = v[(size_t)flat];
   }
-  fclose(fp);
-  return EDM_HIP_OK;
+  return w.write(q, filename, box_min, box_max, b_periodic, b_lammps_format, val, nullptr);
 }
 
 // ---- gaussian grid ------------------------------------------------------------
@@ -972,70 +1014,31 @@ int edm_hip_gauss_update_forces(const edm_hip_gauss *g, long long n, const doubl
   int nblk = 0;
   // (a forces-only call: the workgroups tag their partial energy sums and the host looks at the slots instead of
   //  waiting for the stream, see edm_hip_gauss_pair_forces)
-  const bool poll = n > 0 && edm::forces_poll_enabled();
   edm_hip_gauss *gm = const_cast<edm_hip_gauss *>(g);
-  const unsigned long long tag = poll ? ++gm->force_seq : 0ull;
+  const unsigned long long tag = n > 0 && edm::forces_poll_enabled() ? ++gm->force_seq : 0ull;
   int rc = edm::update_forces_enqueue(g, n, d_x, x_stride, d_f, f_stride, d_mask, apply_mask, &nblk, tag);
   if (rc) return rc;
   if (n <= 0) return EDM_HIP_OK;
-  if (poll) {
-    double e = 0;
-    if (edm::poll_tagged_partials(g, nblk, tag, &e)) {
-      gm->polled_forces++;
-      if (energy) *energy = e;
-      return EDM_HIP_OK;
-    }
-    EDM_HIP_TRY(hipStreamSynchronize(g->stream));   // (the poll ran out: the slots are complete now)
-    e = 0;
-    for (int i = 0; i < nblk; i++) e += g->h_partials[2 * i];
-    if (energy) *energy = e;
-    return EDM_HIP_OK;
-  }
-  EDM_HIP_TRY(hipStreamSynchronize(g->stream));
-  const double e = edm::pair_forces_finish(g, nblk);
-  if (energy) *energy = e;
-  return EDM_HIP_OK;
+  return edm::force_energy(gm, nblk, tag, false, energy);
 }
 
 int edm_hip_gauss_pair_forces(const edm_hip_gauss *g, long long n, const double *d_r, double *d_force,
                               double *energy) {
   if (energy) *energy = 0;
-  int nblk = 0;
-  if (g->g.dim == 1 && n > 0 && edm::forces_poll_enabled()) {
-    // a forces-only call (every fix edm_pair step between two hill steps): the workgroups tag their partial energy
-    // sums, the host looks at the slots instead of waiting for the stream -- the wait's wake-up alone is ~7 us of a
-    // 20 us call.  (The force array is complete when every workgroup's sum is: a workgroup stores its forces first.)
-    edm_hip_gauss *gm = const_cast<edm_hip_gauss *>(g);
-    hipEvent_t e0, e1;
-    profile_slot(g, &e0, &e1);
-    int tagged = 0;
-    const unsigned long long tag = ++gm->force_seq;
-    EDM_HIP_TRY(edm::launch_pair_forces(g->g, g->rec, n, d_r, d_force, g->d_partials, nullptr, g->stream, e0, e1, &nblk, tag, &tagged));
-    if (tagged) {
-      double e = 0;
-      if (edm::poll_tagged_partials(g, nblk, tag, &e)) {
-        gm->polled_forces++;
-        if (energy) *energy = e;
-        return EDM_HIP_OK;
-      }
-      EDM_HIP_TRY(hipStreamSynchronize(g->stream));   // (the poll ran out: the slots are complete now)
-      e = 0;
-      for (int i = 0; i < nblk; i++) e += g->h_partials[2 * i];
-      if (energy) *energy = e;
-      return EDM_HIP_OK;
-    }
-    EDM_HIP_TRY(hipStreamSynchronize(g->stream));
-    const double e = edm::pair_forces_finish(g, nblk);
-    if (energy) *energy = e;
-    return EDM_HIP_OK;
-  }
-  int rc = edm::pair_forces_enqueue(g, n, d_r, d_force, &nblk);
+  edm_hip_gauss *gm = const_cast<edm_hip_gauss *>(g);
+  edm::PendingForces pf;
+  pf.active = true;
+  pf.n = n;
+  pf.d_r = d_r;
+  pf.d_force = d_force;
+  // a forces-only call (every fix edm_pair step between two hill steps): the workgroups tag their partial energy
+  // sums, the host looks at the slots instead of waiting for the stream -- the wait's wake-up alone is ~7 us of a
+  // 20 us call.  (The force array is complete when every workgroup's sum is: a workgroup stores its forces first.)
+  if (g->g.dim == 1 && n > 0 && edm::forces_poll_enabled()) pf.tag = ++gm->force_seq;
+  int rc = edm::pending_forces_flush(g, &pf);
   if (rc) return rc;
   if (n <= 0) return EDM_HIP_OK;
-  EDM_HIP_TRY(hipStreamSynchronize(g->stream));
-  const double e = edm::pair_forces_finish(g, nblk);
-  if (energy) *energy = e;
-  return EDM_HIP_OK;
+  return edm::force_energy(gm, pf.nblk, pf.tagged ? pf.tag : 0, false, energy);
 }
 
 int edm_hip_gauss_wait(edm_hip_gauss *g) {
@@ -1163,7 +1166,7 @@ int faces_prepare(edm_hip_gauss *g, const double **faces) {
 }
 
 // K1 without the host wait: the launch is queued, the per-workgroup energy sums land in host-mapped
-// memory; pair_forces_finish() adds them up after the stream has been synchronised by the caller
+// memory; force_energy() adds them up
 int pair_forces_enqueue(const edm_hip_gauss *g, long long n, const double *d_r, double *d_force, int *nblk) {
   *nblk = 0;
   if (g->g.dim != 1) {
@@ -1176,7 +1179,7 @@ int pair_forces_enqueue(const edm_hip_gauss *g, long long n, const double *d_r, 
   EDM_HIP_TRY(launch_pair_forces(g->g, g->rec, n, d_r, d_force, g->d_partials, nullptr, g->stream, e0, e1, nblk));
   return EDM_HIP_OK;
 }
-// K2 (any dimension, strided rows, group mask) without the host wait; finish with pair_forces_finish()
+// K2 (any dimension, strided rows, group mask) without the host wait; finish with force_energy()
 int update_forces_enqueue(const edm_hip_gauss *g, long long n, const double *d_x, int x_stride, double *d_f, int f_stride,
                           const int *d_mask, int apply_mask, int *nblk, unsigned long long tag) {
   *nblk = 0;
@@ -1268,7 +1271,8 @@ int select_prep_enqueue(const edm_hip_gauss *g, const SelectArgs &a, const HillL
   EDM_HIP_TRY(launch_select_prep(a, g->g, h, g->stream));
   return EDM_HIP_OK;
 }
-// forces-only calls poll their workgroups' tagged sums unless EDM_HIP_POLL=0
+// forces-only calls poll their workgroups' tagged sums, and short hill batches their completion word, unless
+// EDM_HIP_POLL=0
 bool forces_poll_enabled() {
   static int v = -1;
   if (v < 0) {
@@ -1298,22 +1302,27 @@ bool poll_tagged_partials(const edm_hip_gauss *g, int nblk, unsigned long long t
   *energy = e;
   return true;
 }
-double pair_forces_finish(const edm_hip_gauss *g, int nblk) {
+int force_energy(edm_hip_gauss *g, int nblk, unsigned long long tag, bool complete, double *energy,
+                 int (*wait)(void *ctx, int *nblk), void *wait_ctx) {
   double e = 0;
-  for (int i = 0; i < nblk; i++) e += g->h_partials[i];
-  return e;
+  if (tag && !complete && poll_tagged_partials(g, nblk, tag, &e)) {
+    g->polled_forces++;
+  } else {
+    if (wait) {
+      int rc = wait(wait_ctx, &nblk);
+      if (rc) return rc;
+    } else if (!complete) {
+      EDM_HIP_TRY(hipStreamSynchronize(g->stream));
+    }
+    e = 0;
+    for (int i = 0; i < nblk; i++) e += g->h_partials[tag ? 2 * i : i];
+  }
+  if (energy) *energy = e;
+  return EDM_HIP_OK;
 }
 
-// Completion of a short hill batch is seen by polling two words its last kernel writes behind the read-back
-// region (EDM_HIP_POLL=0 in the environment: always wait for the stream instead)
-static bool poll_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("EDM_HIP_POLL");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
-}
+// (completion of a short hill batch is seen by polling two words its last kernel writes behind the read-back region
+//  -- unless EDM_HIP_POLL=0, forces_poll_enabled: then the host always waits for the stream)
 static const long long SMALL_BATCH = 4096;  // read-back of a batch this small is one async burst
 
 // Upper bound on the tiles one hill can mark (k_mark_tiles keeps the tiles of the stencil's bounding box whose
@@ -1373,20 +1382,27 @@ static long long tiles_per_hill_bound(const Geom &q) {
   return best;
 }
 
+// waits (bounded: 2 ms, then for the stream) until the staging buffer's completion word shows the pending read-back
+// region written
+static int wait_pending_region(edm_hip_gauss *g) {
+  volatile unsigned long long *w = reinterpret_cast<volatile unsigned long long *>(g->h_stage + g->h_stage_bytes - 128);
+  const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(2000);
+  for (unsigned spin = 0; w[0] < g->rb_pending_seq; spin++) {
+    __builtin_ia32_pause();
+    if ((spin & 255) == 255 && std::chrono::steady_clock::now() > t_end) {
+      EDM_HIP_TRY(hipStreamSynchronize(g->stream));
+      break;
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return EDM_HIP_OK;
+}
 // the read-back region of a batch released by its header line, copied out of the staging buffer (after its
 // completion word has arrived: normally long ago) so that the next batch can reuse the buffer
 static int save_pending_region(edm_hip_gauss *g) {
   if (!g->rb_pending_seq) return EDM_HIP_OK;
-  volatile unsigned long long *w = reinterpret_cast<volatile unsigned long long *>(g->h_stage + g->h_stage_bytes - 128);
-  const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(2000);
-  bool seen = false;
-  for (unsigned spin = 0;; spin++) {
-    if (w[0] >= g->rb_pending_seq) { seen = true; break; }
-    __builtin_ia32_pause();
-    if ((spin & 255) == 255 && std::chrono::steady_clock::now() > t_end) break;
-  }
-  if (!seen) EDM_HIP_TRY(hipStreamSynchronize(g->stream));
-  std::atomic_thread_fence(std::memory_order_acquire);
+  int rc = wait_pending_region(g);
+  if (rc) return rc;
   g->rb_saved.assign(g->h_stage, g->h_stage + g->rb_pending_bytes);
   g->rb_pending_seq = 0;
   return EDM_HIP_OK;
@@ -1408,16 +1424,8 @@ int apply_hills_fetch_deferred(edm_hip_gauss *g, long long nh_bound, long long n
       set_error("apply_hills_fetch_deferred: no deferred read-back of that shape");
       return EDM_HIP_ERR_STATE;
     }
-    volatile unsigned long long *w = reinterpret_cast<volatile unsigned long long *>(g->h_stage + g->h_stage_bytes - 128);
-    const auto t_end = std::chrono::steady_clock::now() + std::chrono::microseconds(2000);
-    bool seen = false;
-    for (unsigned spin = 0;; spin++) {
-      if (w[0] >= g->rb_pending_seq) { seen = true; break; }
-      __builtin_ia32_pause();
-      if ((spin & 255) == 255 && std::chrono::steady_clock::now() > t_end) break;
-    }
-    if (!seen) EDM_HIP_TRY(hipStreamSynchronize(g->stream));
-    std::atomic_thread_fence(std::memory_order_acquire);
+    int rc = wait_pending_region(g);
+    if (rc) return rc;
     g->rb_pending_seq = 0;
     region = g->h_stage;
   } else {
@@ -1786,7 +1794,7 @@ int apply_hills(edm_hip_gauss *g, const ApplySpec &spec, ApplyOutcome *out, bool
       la.rb_src = ws.rb.p;
       la.rb_dst = g->d_stage;
       rb_pushed = true;
-      if (poll_enabled()) {
+      if (forces_poll_enabled()) {
         la.done_flag = reinterpret_cast<unsigned long long *>(g->d_stage + g->h_stage_bytes - 128);
         la.done_seq = ++g->done_seq;
         polled = true;
@@ -2183,82 +2191,22 @@ int edm_hip_gauss_write(const edm_hip_gauss *g, const char *filename) {
 // without the gaussian boundary handling) and written with their derivative columns.
 static int multi_write_records(const Geom &q, const double *rec, hipStream_t stream, double *scratch, const char *filename,
                                const double *box_min, const double *box_max, const int *b_periodic, int b_lammps_format) {
-  unsigned int counts[3] = {1, 1, 1}, extra_n = 0;
-  if (b_lammps_format) extra_n = (unsigned int)(box_min[0] / q.dx[0]);
-  size_t total = 1;
-  for (int d = 0; d < q.dim; d++) {
-    counts[d] = (unsigned int)(int)ceil((box_max[d] - box_min[d]) / q.dx[d]);
-    counts[d] = b_periodic[d] ? counts[d] : counts[d] + 1;
-    total *= counts[d];
-  }
-  // sample coordinates and the in_grid filter (host geometry only)
-  std::vector<double> xs;
-  std::vector<size_t> which;
-  std::vector<unsigned int> sup0;
-  xs.reserve(total * q.dim);
-  for (size_t i = 0; i < total; i++) {
-    size_t tmp = i, sup[3] = {0, 0, 0};
-    double x[3];
-    int d;
-    for (d = 0; d < q.dim - 1; d++) {
-      sup[d] = tmp % counts[d];
-      tmp = (tmp - sup[d]) / counts[d];
-      x[d] = sup[d] * q.dx[d] + box_min[d];
-    }
-    sup[d] = tmp;
-    x[d] = sup[d] * q.dx[d] + box_min[d];
-    bool in = true;
-    for (d = 0; d < q.dim; d++)
-      if (!q.periodic[d] && (x[d] < q.min[d] || x[d] >= q.max[d] - q.dx[d])) in = false;
-    if (!in) continue;
-    which.push_back(i);
-    sup0.push_back((unsigned int)sup[0]);
-    for (d = 0; d < q.dim; d++) xs.push_back(x[d]);
-  }
-  const size_t m = which.size();
+  const BoxWalk w(q, box_min, box_max, b_periodic, b_lammps_format);
+  const size_t m = w.which.size();
   std::vector<double> E(m), der(m * q.dim);
   if (m) {
     const Geom plain = plain_geom(q);  // DimmedGrid lookup: no boundary test, no remap
-    double *dx = nullptr, *dE = nullptr, *dD = nullptr;
-    EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dx), sizeof(double) * m * q.dim));
-    EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dE), sizeof(double) * m));
-    EDM_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dD), sizeof(double) * m * q.dim));
-    EDM_HIP_TRY(hipMemcpy(dx, xs.data(), sizeof(double) * m * q.dim, hipMemcpyHostToDevice));
+    PointBufs p;
+    EDM_HIP_TRY(p.reserve(m, q.dim));
+    EDM_HIP_TRY(hipMemcpy(p.x.p, w.xs.data(), sizeof(double) * m * q.dim, hipMemcpyHostToDevice));
     LookupArgs a{};
-    a.n = (long long)m; a.x = dx; a.x_stride = q.dim; a.energy = dE; a.f = dD; a.apply_mask = -1;
+    a.n = (long long)m; a.x = p.x.p; a.x_stride = q.dim; a.energy = p.e.p; a.f = p.d.p; a.apply_mask = -1;
     EDM_HIP_TRY(launch_lookup(plain, rec, LOOKUP_VALUES, a, scratch, nullptr, stream));
     EDM_HIP_TRY(hipStreamSynchronize(stream));
-    EDM_HIP_TRY(hipMemcpy(E.data(), dE, sizeof(double) * m, hipMemcpyDeviceToHost));
-    EDM_HIP_TRY(hipMemcpy(der.data(), dD, sizeof(double) * m * q.dim, hipMemcpyDeviceToHost));
-    (void)hipFree(dx);
-    (void)hipFree(dE);
-    (void)hipFree(dD);
+    EDM_HIP_TRY(hipMemcpy(E.data(), p.e.p, sizeof(double) * m, hipMemcpyDeviceToHost));
+    EDM_HIP_TRY(hipMemcpy(der.data(), p.d.p, sizeof(double) * m * q.dim, hipMemcpyDeviceToHost));
   }
-  FILE *fp = fopen(filename, "w");
-  if (!fp) {
-    set_error(std::string("cannot open ") + filename);
-    return EDM_HIP_ERR_IO;
-  }
-  if (!b_lammps_format) {
-    long long bins[3];
-    for (int d = 0; d < q.dim; d++) bins[d] = b_periodic[d] ? (long long)counts[d] : (long long)counts[d] - 1;
-    edm::put_header(fp, 1, q.dim, bins, box_min, box_max, b_periodic);
-  } else {
-    fprintf(fp, "#Auto generated by electronic-dance-music\n\n");
-    fprintf(fp, "EDM\n");
-    fprintf(fp, "N %u R %g %g\n\n", extra_n + counts[0], q.dx[0], box_max[0]);
-    for (size_t i = 1; i < extra_n; i++) fprintf(fp, "%zu %g 0.0 0.0\n", i, i * q.dx[0]);
-  }
-  for (size_t j = 0; j < m; j++) {
-    if (b_lammps_format) fprintf(fp, "%zu ", which[j] + extra_n);
-    for (int d = 0; d < q.dim; d++) fprintf(fp, "%.8f ", xs[j * q.dim + d]);
-    fprintf(fp, "%.8f ", E[j]);
-    for (int d = 0; d < q.dim; d++) fprintf(fp, "%.8f ", -der[j * q.dim + d]);
-    fprintf(fp, "\n");
-    if (sup0[j] == counts[0] - 1) fprintf(fp, "\n");
-  }
-  fclose(fp);
-  return EDM_HIP_OK;
+  return w.write(q, filename, box_min, box_max, b_periodic, b_lammps_format, E, &der);
 }
 
 extern "C" {

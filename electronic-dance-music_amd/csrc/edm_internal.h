@@ -289,10 +289,15 @@ inline void faces_touch(edm_hip_gauss *g) {   // the node records were written b
 int pair_forces_enqueue(const edm_hip_gauss *g, long long n, const double *d_r, double *d_force, int *nblk);
 int update_forces_enqueue(const edm_hip_gauss *g, long long n, const double *d_x, int x_stride, double *d_f, int f_stride,
                           const int *d_mask, int apply_mask, int *nblk, unsigned long long tag = 0);
-double pair_forces_finish(const edm_hip_gauss *g, int nblk);
-// queues pending forces on their own (no-op when none are pending)
 bool forces_poll_enabled();
 bool poll_tagged_partials(const edm_hip_gauss *g, int nblk, unsigned long long tag, double *energy);
+// The energy of a force launch of `nblk` workgroups, added up in workgroup order from the partial sums in h_partials
+// ({sum, tag} slots when `tag` != 0).  Tagged and not `complete`: the slots are polled (polled_forces counts a hit).
+// Otherwise, or when the poll runs out, the host waits -- `wait` when given (it may queue the pass again and change
+// nblk), else for the stream unless `complete` (a polled hill batch has shown the stream past the launch).
+int force_energy(edm_hip_gauss *g, int nblk, unsigned long long tag, bool complete, double *energy,
+                 int (*wait)(void *ctx, int *nblk) = nullptr, void *wait_ctx = nullptr);
+// queues pending forces on their own (no-op when none are pending)
 int pending_forces_flush(const edm_hip_gauss *g, PendingForces *pf);
 // selection (+ preparation / packing) of a step, in one launch with the pending forces where possible
 int select_prep_enqueue(const edm_hip_gauss *g, const SelectArgs &a, const HillList &h, PendingForces *pf);
