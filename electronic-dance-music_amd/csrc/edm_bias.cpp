@@ -375,6 +375,15 @@ struct edm_hip_bias {
   bool ord_on_own_stream = false;   // this step's record / force passes went to ord_stream
   unsigned ord_seq = 0;
   DevBuf<int> ord_first;
+  // a single rank's step with more hills than one pass holds: the force pass in segments (ordered_segments_enqueue)
+  long long ord_segment_hills = 0;   // edm_hip_bias_set("ordered_segment_hills"): hills per segment (0: ordered_max_hills())
+  long long ord_segments = 0;        // edm_hip_bias_get("ordered_segments"): segments of the last reference-order step's
+                                     // force pass (1: one pass, 0: no hill)
+  DevBuf<double> ord_base;           // the records behind the segments so far: two grids, written and read in turn
+  DevBuf<long long> ord_starts;      // first pair of every segment (launch_ordered_segment_starts)
+  DevBuf<int> ord_ahead, ord_first2;   // OrderedForcesArgs::dirty_ahead per segment / first samples 2 k (none given)
+  DevBuf<double> ord_seg_partials;   // the segments' partial energy sums
+  DevBuf<double> ord_ent;            // pair list: every entry's energy and dV/dr, [2][npairs]
   int reference_order = 0;     // edm_hip_bias_set("reference_order"): edm_hip_bias_pair_list_step evaluates its forces in
                                // the reference's order too (edm_hip_bias_pair_step_ordered is that mode's array entry)
   // multi-GPU
@@ -609,6 +618,8 @@ int edm_hip_bias_destroy(edm_hip_bias *b) {
   if (b->h_count) (void)hipHostFree(b->h_count);
   b->stage_x.release(); b->stage_u.release(); b->stage_h.release(); b->tail_w.release(); b->hx0.release();
   b->ord_terms.release(); b->ord_range.release(); b->ord_rec0.release(); b->ord_records.release(); b->ord_counts.release(); b->ord_dirty.release(); b->ord_first.release();
+  b->ord_base.release(); b->ord_starts.release(); b->ord_ahead.release(); b->ord_first2.release(); b->ord_seg_partials.release();
+  b->ord_ent.release();
   delete b;
   return EDM_HIP_OK;
 }
@@ -879,6 +890,7 @@ static int exchange_hills(edm_hip_bias *b, long long nh_local, const double *d_x
 static void ordered_snapshot_ride(edm_hip_bias *b, SelectArgs *a);
 static int ordered_snapshot_now(edm_hip_bias *b);
 static int ordered_forces_enqueue(edm_hip_bias *b);
+static long long ordered_segment_cap(const edm_hip_bias *b);
 static int process_new_hills(edm_hip_bias *b, long long n, const double *d_x, int x_stride, const double *d_ru,
                              int apply_mask) {
   if (n <= 0 && !b->comm) return EDM_HIP_OK;  // with a communicator every rank must reach the exchange
@@ -1186,7 +1198,8 @@ static int process_new_hills(edm_hip_bias *b, long long n, const double *d_x, in
     long long pack_bound;
   } early_ctx{b, this_h, d_sel, nh, packed_exchange, pack_bound};
   b->ord_on_own_stream = false;
-  if (b->ord_early.armed && deferred_bound && (packed_exchange || !b->comm)) {
+  // (a single rank's batch that may hold more hills than one segment: its force pass goes out behind the batch, in segments)
+  if (b->ord_early.armed && deferred_bound && (packed_exchange || !b->comm) && (b->comm || nh <= ordered_segment_cap(b))) {
     if (spec.ord_terms && !b->bias->shared_device && !b->ord_own_stream_off) {
       // a rank with the device to itself: record and force pass on their own stream, beside the batch's launch
       if (!b->ord_stream) {
@@ -1617,13 +1630,136 @@ static int ordered_records_enqueue(edm_hip_bias *b, OrderedForcesArgs *out) {
   return EDM_HIP_OK;
 }
 
-// records of the batch's hills, then the force pass that reads them (b->last_batch, b->ord_early: the pairs)
+static long long ordered_segment_cap(const edm_hip_bias *b) {
+  return b->ord_segment_hills > 0 ? b->ord_segment_hills : ordered_max_hills();
+}
+
+// A single rank's step with more hills than one pass holds (ordered_segment_cap): the batch's hills are cut into segments
+// [H_s, H_s+1) of that many.  Per segment, on the object's stream: the record pass over its hills from the records behind
+// the segments before it (the previous pass's rec_end; the grid's step-start copy for the first), which leaves the
+// records behind its own last hill for the next; then the force pass over the pairs whose hill count lies in the segment
+// -- a contiguous run, found on the device and read back once.  A pair list's entries store their terms per segment,
+// one per-atom pass sums them at the end.  The arithmetic is a single pass's: the forces do not depend on the segments.
+static int ordered_segments_enqueue(edm_hip_bias *b) {
+  edm_hip_gauss *g = b->bias;
+  hipStream_t s = g->stream;
+  edm_hip_bias::OrderedEarly &oe = b->ord_early;
+  const long long nh = b->last_batch.nh, seg = ordered_segment_cap(b);
+  const long long nseg_ll = (nh + seg - 1) / seg;
+  if (nseg_ll > INT_MAX / 2) {
+    set_error("reference-order pair step: too many hill segments");
+    return EDM_HIP_ERR_ARG;
+  }
+  const int nseg = (int)nseg_ll;
+  const long long n = oe.list ? oe.pl.npairs : oe.n;
+  long long cap = 256;
+  while (cap < seg) cap *= 2;
+  if (cap > ordered_max_hills()) cap = ordered_max_hills();
+  const size_t grid_doubles = (size_t)g->g.total * 2;
+  EDM_HIP_TRY(b->ord_records.reserve(ordered_record_doubles(g->g, cap)));
+  EDM_HIP_TRY(b->ord_counts.reserve(ordered_count_shorts(g->g, cap)));
+  EDM_HIP_TRY(b->ord_dirty.reserve_zeroed((size_t)(nh > 4096 ? nh : 4096)));
+  EDM_HIP_TRY(b->ord_base.reserve(2 * grid_doubles));
+  EDM_HIP_TRY(b->ord_ahead.reserve((size_t)nseg));
+  EDM_HIP_TRY(b->ord_starts.reserve((size_t)nseg + 2));
+  const int *first = nullptr;
+  if (!oe.list) {
+    first = oe.d_first;
+    if (!first) {   // (pair k's first add_hill call is 2 k: the segments' force passes need it as an array)
+      EDM_HIP_TRY(b->ord_first2.reserve((size_t)(n > 0 ? n : 1)));
+      EDM_HIP_TRY(launch_twice_index(b->ord_first2.p, n, s));
+      first = b->ord_first2.p;
+    }
+  }
+  EDM_HIP_TRY(launch_ordered_segment_starts(b->last_batch.sel, nh, seg, nseg, first, n, b->ord_starts.p, s));
+  std::vector<long long> starts((size_t)nseg + 2);
+  EDM_HIP_TRY(hipMemcpyAsync(starts.data(), b->ord_starts.p, sizeof(long long) * starts.size(), hipMemcpyDeviceToHost, s));
+  EDM_HIP_TRY(hipStreamSynchronize(s));
+  if (starts[(size_t)nseg + 1]) {
+    set_error("reference-order pair step: a step with more hills than one segment needs first-sample indices that ascend "
+              "with the pair index (the fix's pair order)");
+    return EDM_HIP_ERR_ARG;
+  }
+  OrderedForcesArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nh_cap = cap;
+  a.k = b->last_batch.k;
+  a.heights = b->last_batch.heights;
+  a.h_const = b->last_batch.h_const;
+  a.tail_h1 = b->last_batch.tail_h1;
+  a.tail_h2 = b->last_batch.tail_h2;
+  a.hx = g->ws.hx.p;
+  a.hc = g->ws.hc.p;
+  a.ht = g->ws.ht.p;
+  a.sel = b->last_batch.sel;
+  a.records = b->ord_records.p;
+  a.counts = b->ord_counts.p;
+  a.dirty_hill = b->ord_dirty.p;
+  if (b->last_batch.terms_emitted) {   // (the emitters of the batch's launch noted the dirty hills under this number)
+    a.terms = b->ord_terms.p;
+    a.terms_rows = b->ord_terms_rows;
+    a.dirty_seq = b->ord_seq;
+  } else {
+    a.dirty_seq = ++b->ord_seq;   // (one number for all segments: a segment reads the notes of those before it)
+  }
+  a.form_n = n;
+  if (oe.list)
+    EDM_HIP_TRY(b->ord_ent.reserve((size_t)2 * (size_t)(n > 0 ? n : 1)));
+  else
+    EDM_HIP_TRY(b->ord_seg_partials.reserve((size_t)ordered_segment_partials(n, nseg)));
+  double *const base[2] = {b->ord_base.p, b->ord_base.p + grid_doubles};
+  long long nparts = 0;
+  for (int q = 0; q < nseg; q++) {
+    const long long h0 = (long long)q * seg, h1 = (h0 + seg < nh) ? h0 + seg : nh;
+    a.nh = h1 - h0;
+    a.hill_off = h0;
+    a.sel_off = h0;
+    a.rec0 = q == 0 ? b->ord_rec0.p : base[(q - 1) & 1];
+    a.rec_end = q + 1 < nseg ? base[q & 1] : nullptr;
+    a.dirty_ahead = b->ord_ahead.p + q;
+    a.dirty_ahead_prev = q > 0 ? b->ord_ahead.p + q - 1 : nullptr;
+    a.dirty_prev_off = q > 0 ? h0 - seg : 0;
+    EDM_HIP_TRY(launch_ordered_records(g->g, g->tables(), a, s));
+    const long long p0 = starts[(size_t)q], p1 = starts[(size_t)q + 1];
+    if (p1 <= p0) continue;
+    if (oe.list) {
+      EDM_HIP_TRY(launch_pairlist_entries_ordered(g->g, oe.pl, a, p0, p1, b->ord_ent.p, b->ord_ent.p + n, s));
+      continue;
+    }
+    a.n = p1 - p0;
+    a.r = oe.d_r + p0;
+    a.first_sample = first + p0;
+    a.force = oe.d_force + p0;
+    int nb = 0;
+    EDM_HIP_TRY(launch_pair_forces_ordered(g->g, a, b->ord_seg_partials.p + nparts, s, &nb, 0));
+    nparts += nb;
+  }
+  // (the energy: untagged partial sums, which the host reads behind its wait for the stream)
+  oe.tag = 0;
+  if (oe.list) {
+    PairListArgs pl = oe.pl;
+    pl.partial_tag = 0;
+    EDM_HIP_TRY(launch_pairlist_forces_stored(pl, b->ord_ent.p, b->ord_ent.p + n, g->d_partials, s, &oe.nblk));
+  } else {
+    EDM_HIP_TRY(launch_sum_partials(b->ord_seg_partials.p, nparts, g->d_partials, s));
+    oe.nblk = 1;
+  }
+  b->ord_segments = nseg;
+  return EDM_HIP_OK;
+}
+
+// records of the batch's hills, then the force pass that reads them (b->last_batch, b->ord_early: the pairs) -- in
+// segments where a single rank's batch holds more hills than one pass
 static int ordered_forces_enqueue(edm_hip_bias *b) {
   edm_hip_gauss *g = b->bias;
+  if (!b->comm && !b->last_batch.range_dev && b->last_batch.local_cnt < 0 && !b->last_batch.res_dev && !b->last_batch.wait_flag &&
+      b->last_batch.nh > ordered_segment_cap(b))
+    return ordered_segments_enqueue(b);
   hipStream_t s = b->ord_on_own_stream ? b->ord_stream : g->stream;
   OrderedForcesArgs a;
   int rc = ordered_records_enqueue(b, &a);
   if (rc) return rc;
+  b->ord_segments = 1;
   if (b->ord_early.list) {
     PairListArgs pl = b->ord_early.pl;
     pl.partial_tag = b->ord_early.tag;
@@ -1690,7 +1826,9 @@ static int ordered_step_finish(edm_hip_bias *b, int rc, double *energy) {
   }
   int nblk = 0;
   unsigned long long tag = 0;   // (of the pass whose sums are read; a redone step has taken a fresh one)
+  b->ord_segments = 0;
   if (oe.done) {
+    b->ord_segments = (b->last_batch.valid && b->last_batch.nh > 0) ? 1 : 0;
     // (the batch's deferred log lines -- positions and per-hill bias from the read-back region -- are picked up NOW, while
     //  the record and force pass run: at the start of the next cycle, where they would be fetched otherwise, they sit in
     //  front of its first launch, ~2 us)
@@ -2294,6 +2432,8 @@ int edm_hip_bias_get(const edm_hip_bias *b, const char *name, double *value) {
   G("reference_order", b->reference_order)
   G("ord_gate_giveups", b->ord_gate_giveups)
   G("host_add_threads", b->host_add_threads)
+  G("ordered_segment_hills", b->ord_segment_hills)
+  G("ordered_segments", b->ord_segments)
 #undef G
   set_error(std::string("unknown EDMBias member ") + name);
   return EDM_HIP_ERR_ARG;
@@ -2315,6 +2455,14 @@ int edm_hip_bias_set(edm_hip_bias *b, const char *name, double value) {
   if (strcmp(name, "host_add_threads") == 0) {
     if (value < 1 || value > 64) return EDM_HIP_ERR_ARG;
     b->host_add_threads = (int)value;
+    return EDM_HIP_OK;
+  }
+  if (strcmp(name, "ordered_segment_hills") == 0) {   // (0: the default, ordered_max_hills())
+    if (!(value >= 0 && value <= (double)ordered_max_hills())) {
+      set_error("ordered_segment_hills: 0 (the default) to 16384");
+      return EDM_HIP_ERR_ARG;
+    }
+    b->ord_segment_hills = (long long)value;
     return EDM_HIP_OK;
   }
   if (strcmp(name, "debug_tiles_first") == 0 && b->bias) { b->bias->debug_tiles_first = (int)value; return EDM_HIP_OK; }

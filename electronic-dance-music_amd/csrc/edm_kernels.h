@@ -131,7 +131,8 @@ hipError_t launch_pair_forces(const Geom &g, const double *rec, long long n, con
 //       after every hill with a non-zero correction) is applied on the fly: an outward copy node reads the value of
 //       its source node at the same m once the first such hill (first_dirty, found by the record pass) lies before
 //       the pair.
-// 1-D grids only (fix_edm_pair.cpp:52), stencil not wider than a periodic grid, at most ordered_max_hills() hills.
+// 1-D grids only (fix_edm_pair.cpp:52), stencil not wider than a periodic grid, at most ordered_max_hills() hills per pass
+// (a single rank's longer step runs in segments, see launch_ordered_segment_starts).
 struct LimitResult;
 struct OrderedForcesArgs {
   long long nh;             // this rank's hills of the step's batch (true count; unused with range_dev)
@@ -178,6 +179,16 @@ struct OrderedForcesArgs {
   const int *first_sample;  // [n] sample index of pair k's first add_hill call, or NULL: 2 k (the virtual samples of a
                             // device-resident neighbour list)
   double *force;            // [n] out: -dV/dr
+  // one SEGMENT of a single-rank step with more hills than one pass holds (edm_bias.cpp, ordered_segments_enqueue): the
+  // passes cover the batch's hills [hill_off, hill_off + nh), and rec0 holds the records behind the hills ahead of them
+  long long sel_off;        // hill j of the pass has sample index sel[sel_off + j] (no sel: sel_off + j)
+  double *rec_end;          // record pass, optional: out [nodes][2], the running records behind the pass's last hill
+                            // (the next segment's rec0)
+  int *dirty_ahead;         // record pass writes, force pass reads (optional): 1 when a hill ahead of hill_off met a
+                            // non-zero boundary correction -- *dirty_ahead_prev (NULL: 0) or one of [dirty_prev_off, hill_off)
+  const int *dirty_ahead_prev;
+  long long dirty_prev_off;
+  long long form_n;         // force pass: the pair count that chooses the kernel form (0: n) -- the step's, for a segment
 };
 size_t ordered_record_doubles(const Geom &g, long long nh_cap);
 size_t ordered_count_shorts(const Geom &g, long long nh_cap);
@@ -192,6 +203,26 @@ hipError_t launch_pair_forces_ordered(const Geom &g, const OrderedForcesArgs &a,
 // "pair" e, its first sample 2 e; pl.fdelta receives the per-atom sums, pl.partial_tag as in launch_pairlist_forces)
 hipError_t launch_pairlist_forces_ordered(const Geom &g, const PairListArgs &pl, const OrderedForcesArgs &a, double *partials,
                                           hipStream_t s, int *blocks_out);
+// ---- the same in segments of at most ordered_max_hills() hills (a single rank, any number of hills) -----------------
+// The batch's hills [H_s, H_s+1) form segment s, H_s = s * seg.  A pair belongs to the segment that holds the hill count m
+// its force reads (the last segment also takes m = nh), so with ascending first-sample indices the pairs of a segment
+// are a contiguous run: starts[s] = its first pair (first_sample NULL: pair k's first sample is 2 k), starts[nseg] = n,
+// starts[nseg + 1] = 1 when first_sample does not ascend (0 otherwise).  starts: nseg + 2 device words.
+hipError_t launch_ordered_segment_starts(const long long *sel, long long nh, long long seg, int nseg, const int *first_sample,
+                                         long long n, long long *starts, hipStream_t s);
+// first_sample[k] = 2 k (the host entry without first-sample indices)
+hipError_t launch_twice_index(int *out, long long n, hipStream_t s);
+// partial energy sums the segments' force passes leave (at most this many, n pairs in all) ...
+long long ordered_segment_partials(long long n, long long nseg);
+// ... added up in index order into out[0]
+hipError_t launch_sum_partials(const double *partials, long long n, double *out, hipStream_t s);
+// a device-resident list in segments: per segment, the entries [e0, e1) store their energy and dV/dr (ent_v, ent_d:
+// [npairs]); then one per-atom pass sums the stored terms exactly like launch_pairlist_forces_ordered sums the terms
+// it computes (same lanes, same order, same tree) into pl.fdelta and partials[0 .. *blocks_out)
+hipError_t launch_pairlist_entries_ordered(const Geom &g, const PairListArgs &pl, const OrderedForcesArgs &a, long long e0,
+                                           long long e1, double *ent_v, double *ent_d, hipStream_t s);
+hipError_t launch_pairlist_forces_stored(const PairListArgs &pl, const double *ent_v, const double *ent_d, double *partials,
+                                         hipStream_t s, int *blocks_out);
 
 // ---- record layout conversion ---------------------------------------------------
 hipError_t launch_pack(const Geom &g, double *rec, const double *values, const double *derivs, hipStream_t s);

@@ -4914,6 +4914,15 @@ __device__ __forceinline__ void ordered_batch_counts(const OrderedForcesArgs &a,
   if (nloc > a.nh_cap) nloc = a.nh_cap;
   if (nloc < 0) nloc = 0;
 }
+// sample index of hill j of the pass (OrderedForcesArgs::sel_off)
+__device__ __forceinline__ int ordered_sample(const OrderedForcesArgs &a, long long j) {
+  return a.sel ? (int)a.sel[a.sel_off + j] : (int)(a.sel_off + j);
+}
+// the position in the pass from which on an outward copy node reads its source: the pass's own first hill with a
+// non-zero boundary correction, or -1 -- every position -- when a hill ahead of the pass (an earlier segment's) met one
+__device__ __forceinline__ int ordered_first_dirty(const OrderedForcesArgs &a, int own) {
+  return (a.dirty_ahead && *a.dirty_ahead) ? -1 : own;
+}
 long long ordered_max_hills() { return ORD_MAX_HILLS; }
 long long ordered_tiles(const Geom &g) { return (g.n[0] + ORD_NODES - 1) / ORD_NODES; }
 size_t ordered_record_doubles(const Geom &g, long long nh_cap) {
@@ -5002,6 +5011,17 @@ __global__ void __launch_bounds__(BLOCK) k_ordered_records(Geom g, Tables t, Ord
     }
   } else {
     ordered_batch_counts(a, off, nloc, k_split, false);
+    if (a.dirty_ahead && tile == 0) {
+      // (a segment: did a hill ahead of it meet a non-zero boundary correction -- the previous segments' record passes,
+      //  or the batch's emitters, have noted theirs by now)
+      __shared__ int s_any;
+      if (threadIdx.x == 0) s_any = (a.dirty_ahead_prev && *a.dirty_ahead_prev) ? 1 : 0;
+      __syncthreads();
+      for (long long h = a.dirty_prev_off + threadIdx.x; h < a.hill_off; h += BLOCK)
+        if (a.dirty_hill[h] == a.dirty_seq) s_any = 1;   // (every writer stores the same value)
+      __syncthreads();
+      if (threadIdx.x == 0) *a.dirty_ahead = s_any;
+    }
   }
   for (long long base = 0; base < nloc; base += ORD_CHUNK) {
     const int cnt = (nloc - base < ORD_CHUNK) ? (int)(nloc - base) : ORD_CHUNK;
@@ -5150,6 +5170,8 @@ __global__ void __launch_bounds__(BLOCK) k_ordered_records(Geom g, Tables t, Ord
     listed += nl;
     __syncthreads();
   }
+  // (a segment: the records behind its last hill start the next one -- the same running sums a single pass would carry on)
+  if (a.rec_end && in_grid && part == 0) reinterpret_cast<double2 *>(a.rec_end)[n] = make_double2(acc0, acc1);
 }
 
 // One wave that waits for the limiter's word of a batch and then for every emitter's flag: queued ahead of a record pass
@@ -5248,7 +5270,7 @@ __device__ __forceinline__ void ordered_common_init(const Geom &g, const Ordered
   long long off, nloc, k_split;
   ordered_batch_counts(a, off, nloc, k_split);
   oc.H = (int)nloc;
-  for (int i = threadIdx.x; i < oc.H; i += blockDim.x) s_samples[i] = a.sel ? (int)a.sel[i] : i;
+  for (int i = threadIdx.x; i < oc.H; i += blockDim.x) s_samples[i] = ordered_sample(a, i);
   __syncthreads();
   oc.samples = s_samples;
   oc.ntiles = (g.n[0] + ORD_NODES - 1) / ORD_NODES;
@@ -5260,7 +5282,7 @@ __device__ __forceinline__ void ordered_common_init(const Geom &g, const Ordered
     for (int i = threadIdx.x; i < oc.H; i += blockDim.x)
       if (a.dirty_hill[off + i] == a.dirty_seq) atomicMin(&s_fd, i);
     __syncthreads();
-    oc.first_dirty = s_fd;
+    oc.first_dirty = ordered_first_dirty(a, s_fd);
   }
   oc.lo_t = oc.lo_s = oc.hi_t = oc.hi_s = -1;
   if (!g.bper[0]) {   // duplicate_boundary_lanes' cases 0 and 3 in one dimension
@@ -5457,7 +5479,7 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_ordered(Geom g, OrderedFo
     oc.H = (int)nloc;
     int my_first = INT_MAX;   // the first of THIS RANK'S hills with a non-zero boundary correction (position in its slice)
     for (int k = threadIdx.x; k < oc.H; k += blockDim.x) {
-      s_samples[k] = a.sel ? (int)a.sel[k] : k;
+      s_samples[k] = ordered_sample(a, k);
       if (a.dirty_hill[off + k] == a.dirty_seq && k < my_first) my_first = k;
     }
     if (threadIdx.x == 0) s_fd = INT_MAX;
@@ -5489,7 +5511,7 @@ __global__ void __launch_bounds__(BLOCK) k_pair_forces_ordered(Geom g, OrderedFo
     for (int e = threadIdx.x; e < nrows * oc.ntiles; e += BLOCK) s_rows[e] = a.counts[(long long)row0 * oc.ntiles + e];
   }
   __syncthreads();
-  oc.first_dirty = s_fd;
+  oc.first_dirty = ordered_first_dirty(a, s_fd);
   const bool lean = oc.fast && nrows == row1 - row0 + 1 &&
                     (long long)oc.ntiles * a.nh_cap * ORD_NODES < (1ll << 31);   // (32-bit record offsets)
   OrderedLean L;
@@ -5667,7 +5689,7 @@ __global__ void __launch_bounds__(FAST_BLOCK) k_pair_forces_ordered_win(Geom g, 
     oc.H = (int)nloc;
     int my_first = INT_MAX;
     for (int k = threadIdx.x; k < oc.H; k += FAST_BLOCK) {
-      s_samples[k] = a.sel ? (int)a.sel[k] : k;
+      s_samples[k] = ordered_sample(a, k);
       if (a.dirty_hill[off + k] == a.dirty_seq && k < my_first) my_first = k;
     }
     if (threadIdx.x == 0) s_fd = INT_MAX;
@@ -5689,7 +5711,7 @@ __global__ void __launch_bounds__(FAST_BLOCK) k_pair_forces_ordered_win(Geom g, 
     oc.fast = true;   // (the launcher took this kernel for an interpolating, non-periodic 1-D grid)
     oc.inv_dx = 1.0 / g.dx[0];
     __syncthreads();
-    oc.first_dirty = s_fd;
+    oc.first_dirty = ordered_first_dirty(a, s_fd);
   }
   int row0 = 0, row1 = -1;
   if (beg < end) {
@@ -5861,7 +5883,13 @@ hipError_t launch_pair_forces_ordered(const Geom &g, const OrderedForcesArgs &a,
   // (hills per workgroup's run: a pass and ~125 KB of window each -- 2048 hills over 256 runs are nine passes of a few
   //  microseconds beside a run's 100+ us of lookups)
   // (at W1's 1 M pairs the window form is slower: the step 71 against 59 us -- K1's own break-even is ~1.5 M pairs too)
-  if (win_env && a.n >= PAIR_LDS_THRESHOLD && pair_fast_path(g) && a.nh_cap <= ORD_WIN_HILLS) {
+  // (a segment of a longer step, OrderedForcesArgs::form_n: the step's pair count decides; its arrays start where the
+  //  segment's pairs do, and the window form's paired loads and stores want them 16-byte aligned -- else the short form,
+  //  which computes the same forces)
+  const long long form_n = a.form_n ? a.form_n : a.n;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(a.r) | reinterpret_cast<uintptr_t>(a.force)) & 15) == 0 &&
+                       (reinterpret_cast<uintptr_t>(a.first_sample) & 7) == 0;
+  if (win_env && form_n >= PAIR_LDS_THRESHOLD && pair_fast_path(g) && a.nh_cap <= ORD_WIN_HILLS && aligned) {
     const int blocks = cu_count();
     const long long per_block = (((a.n + blocks - 1) / blocks) + 1) & ~1LL;   // (even: two pairs per thread and trip)
     const int wn = g.n[0] < ORD_WIN_NODES ? g.n[0] : ORD_WIN_NODES;
@@ -5953,13 +5981,8 @@ struct OrderedListLookup {
     ordered_lookup_m(g, a, oc, x, m, v, d);
   }
 };
-__global__ void __launch_bounds__(BLOCK) k_pairlist_forces_ordered(Geom g, PairListArgs pl, OrderedForcesArgs a, DupPlan dp,
-                                                                   double *__restrict__ partials) {
-  extern __shared__ int s_samples[];
-  if (a.wait_flag && *a.status == 2) return;   // (as k_pair_forces_ordered)
-  OrderedCommon oc;
-  ordered_common_init(g, a, dp, s_samples, oc);
-  OrderedListLookup ord{g, a, oc};
+__device__ __forceinline__ void ordered_list_lookup_init(OrderedListLookup &ord, const Geom &g, const OrderedForcesArgs &a,
+                                                         const OrderedCommon &oc) {
   ord.ntiles = oc.ntiles;
   ord.nh_cap = (int)a.nh_cap;
   ord.lean = oc.fast && (long long)oc.ntiles * a.nh_cap * ORD_NODES < (1ll << 31);   // (32-bit record offsets)
@@ -5968,6 +5991,15 @@ __global__ void __launch_bounds__(BLOCK) k_pairlist_forces_ordered(Geom g, PairL
   ord.lo_ok = fmax(g.bmin[0], g.min[0]);
   ord.hi_open = fmin(nextafter(g.bmax[0], 1.0e308), g.max[0] - g.dx[0]);
   ord.eps = 1e-11 * fmax(1.0, (double)g.n[0]);
+}
+__global__ void __launch_bounds__(BLOCK) k_pairlist_forces_ordered(Geom g, PairListArgs pl, OrderedForcesArgs a, DupPlan dp,
+                                                                   double *__restrict__ partials) {
+  extern __shared__ int s_samples[];
+  if (a.wait_flag && *a.status == 2) return;   // (as k_pair_forces_ordered)
+  OrderedCommon oc;
+  ordered_common_init(g, a, dp, s_samples, oc);
+  OrderedListLookup ord{g, a, oc};
+  ordered_list_lookup_init(ord, g, a, oc);
   pairlist_forces_body<false, OrderedListLookup>(g, a.rec0, pl, partials, 0.0, blockIdx.x, gridDim.x, &ord);
 }
 hipError_t launch_pairlist_forces_ordered(const Geom &g, const PairListArgs &pl, const OrderedForcesArgs &a, double *partials,
@@ -5988,6 +6020,130 @@ hipError_t launch_pairlist_forces_ordered(const Geom &g, const PairListArgs &pl,
   }
   const size_t lds = sizeof(int) * (size_t)(((a.range_dev || a.res_dev) ? a.nh_cap : a.nh) > 0 ? ((a.range_dev || a.res_dev) ? a.nh_cap : a.nh) : 1);
   hipLaunchKernelGGL(k_pairlist_forces_ordered, dim3((unsigned)nb), dim3(BLOCK), lds, s, g, pl, a, dp, partials);
+  if (blocks_out) *blocks_out = (int)nb;
+  return hipGetLastError();
+}
+
+// ---- a single rank's step in segments of hills (OrderedForcesArgs::sel_off, edm_bias.cpp: ordered_segments_enqueue) ----
+// segment s's first pair: the first whose first sample lies beyond hill H_s - 1's (so that it reads m >= H_s); one thread
+// per segment boundary, a binary search each -- and the whole grid checks that the indices ascend
+__global__ void __launch_bounds__(BLOCK) k_ordered_segment_starts(const long long *__restrict__ sel, long long nh, long long seg,
+                                                                  int nseg, const int *__restrict__ first_sample, long long n,
+                                                                  long long *__restrict__ starts) {
+  const long long t = (long long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t <= nseg) {
+    long long lo = 0;
+    if (t == nseg) {
+      lo = n;
+    } else if (t > 0) {
+      const long long h = t * seg - 1;
+      const long long last = sel ? sel[h] : h;
+      long long hi = n;
+      while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        const long long fs = first_sample ? (long long)first_sample[mid] : 2 * mid;
+        if (fs <= last) lo = mid + 1; else hi = mid;
+      }
+    }
+    starts[t] = lo;
+  }
+  if (first_sample) {
+    const long long stride = (long long)gridDim.x * BLOCK;
+    for (long long k = t + 1; k < n; k += stride)
+      if (first_sample[k] < first_sample[k - 1]) starts[nseg + 1] = 1;   // (every writer stores the same value)
+  }
+}
+hipError_t launch_ordered_segment_starts(const long long *sel, long long nh, long long seg, int nseg, const int *first_sample,
+                                         long long n, long long *starts, hipStream_t s) {
+  if (nseg < 1 || seg < 1 || (long long)(nseg - 1) * seg >= nh || (long long)nseg * seg < nh || n < 0) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(starts + nseg + 1, 0, sizeof(long long), s);
+  if (e != hipSuccess) return e;
+  long long nb = ((first_sample ? n : 0) + BLOCK - 1) / BLOCK;
+  const long long nb_seg = (nseg + 1 + BLOCK - 1) / BLOCK;
+  if (nb > MAX_BLOCKS) nb = MAX_BLOCKS;
+  if (nb < nb_seg) nb = nb_seg;
+  hipLaunchKernelGGL(k_ordered_segment_starts, dim3((unsigned)nb), dim3(BLOCK), 0, s, sel, nh, seg, nseg, first_sample, n, starts);
+  return hipGetLastError();
+}
+__global__ void __launch_bounds__(BLOCK) k_twice_index(int *__restrict__ out, long long n) {
+  const long long stride = (long long)gridDim.x * BLOCK;
+  for (long long k = (long long)blockIdx.x * BLOCK + threadIdx.x; k < n; k += stride) out[k] = (int)(2 * k);
+}
+hipError_t launch_twice_index(int *out, long long n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  long long nb = (n + BLOCK - 1) / BLOCK;
+  if (nb > MAX_BLOCKS) nb = MAX_BLOCKS;
+  hipLaunchKernelGGL(k_twice_index, dim3((unsigned)nb), dim3(BLOCK), 0, s, out, n);
+  return hipGetLastError();
+}
+// (a force pass of n_s pairs takes at most max(cu_count(), ceil(n_s / (4 BLOCK))) workgroups, see launch_pair_forces_ordered)
+long long ordered_segment_partials(long long n, long long nseg) {
+  return nseg * ((long long)cu_count() + 1) + n / (4 * BLOCK) + 1;
+}
+hipError_t launch_sum_partials(const double *partials, long long n, double *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(BLOCK), 0, s, partials, n, out);
+  return hipGetLastError();
+}
+// a list segment's entries: energy and dV/dr of each, read exactly as k_pairlist_forces_ordered reads them (same
+// distance expression as pairlist_side's, same lookup)
+__global__ void __launch_bounds__(BLOCK) k_pairlist_entries_ordered(Geom g, PairListArgs pl, OrderedForcesArgs a, DupPlan dp,
+                                                                    long long e0, long long e1, double *__restrict__ ent_v,
+                                                                    double *__restrict__ ent_d) {
+  extern __shared__ int s_samples[];
+  OrderedCommon oc;
+  ordered_common_init(g, a, dp, s_samples, oc);
+  OrderedListLookup ord{g, a, oc};
+  ordered_list_lookup_init(ord, g, a, oc);
+  const long long stride = (long long)gridDim.x * BLOCK;
+  for (long long e = e0 + (long long)blockIdx.x * BLOCK + threadIdx.x; e < e1; e += stride) {
+    double delx, dely, delz, v, d;
+    const double r = pairlist_distance(pl.x, pl.pair_i[e], pl.pair_j[e], delx, dely, delz);
+    ord.lookup(r, (int)e, v, d);
+    ent_v[e] = v;
+    ent_d[e] = d;
+  }
+}
+hipError_t launch_pairlist_entries_ordered(const Geom &g, const PairListArgs &pl, const OrderedForcesArgs &a, long long e0,
+                                           long long e1, double *ent_v, double *ent_d, hipStream_t s) {
+  if (!ordered_forces_supported(g) || a.nh_cap > ORD_MAX_HILLS || a.nh > a.nh_cap || e0 < 0 || e1 > pl.npairs) return hipErrorInvalidValue;
+  if (e1 <= e0) return hipSuccess;
+  long long nb = (e1 - e0 + BLOCK - 1) / BLOCK;
+  if (nb > MAX_BLOCKS) nb = MAX_BLOCKS;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pairlist_entries_ordered),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int) * ORD_MAX_HILLS));
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  const size_t lds = sizeof(int) * (size_t)(a.nh > 0 ? a.nh : 1);
+  hipLaunchKernelGGL(k_pairlist_entries_ordered, dim3((unsigned)nb), dim3(BLOCK), lds, s, g, pl, a, make_dup_plan(g), e0, e1, ent_v,
+                     ent_d);
+  return hipGetLastError();
+}
+// ... and the per-atom sums of the stored terms: pairlist_forces_body with a lookup that reads them back
+struct StoredListLookup {
+  const double *v, *d;
+  __device__ __forceinline__ void lookup(double, int entry, double &vv, double &dd) const {
+    vv = v[entry];
+    dd = d[entry];
+  }
+};
+__global__ void __launch_bounds__(BLOCK) k_pairlist_forces_stored(Geom g, PairListArgs pl, StoredListLookup st,
+                                                                  double *__restrict__ partials) {
+  pairlist_forces_body<false, StoredListLookup>(g, nullptr, pl, partials, 0.0, blockIdx.x, gridDim.x, &st);
+}
+hipError_t launch_pairlist_forces_stored(const PairListArgs &pl, const double *ent_v, const double *ent_d, double *partials,
+                                         hipStream_t s, int *blocks_out) {
+  if (!pl.it_entry || !pl.jt_entry) return hipErrorInvalidValue;
+  if (blocks_out) *blocks_out = 0;
+  if (pl.nall <= 0) return hipSuccess;
+  const long long threads = (long long)pl.nall * 16;   // (the grid of launch_pairlist_forces_ordered)
+  long long nb = (threads + BLOCK - 1) / BLOCK;
+  if (nb > MAX_BLOCKS) nb = MAX_BLOCKS;
+  Geom g;
+  memset(&g, 0, sizeof(g));   // (unused: the terms are read back, not looked up)
+  hipLaunchKernelGGL(k_pairlist_forces_stored, dim3((unsigned)nb), dim3(BLOCK), 0, s, g, pl, StoredListLookup{ent_v, ent_d}, partials);
   if (blocks_out) *blocks_out = (int)nb;
   return hipGetLastError();
 }

@@ -350,8 +350,13 @@ int edm_hip_bias_pair_step_host(edm_hip_bias *b, long long n, const double *h_r,
  * the number of add_hill calls issued before pair k's update_force.  With a communicator a rank's pairs see the hills
  * of THAT RANK'S earlier add_hill calls -- the reference's ranks replay each other's hills in post_add_hill only
  * (edm_bias.cpp:565-583, :630-706).  The force pass keeps, per 32-node tile of the grid, the
- * tile's records behind every hill that reached it (~3 MB for the ~125 hills of a 1 M-pair step): at most 16 384 hills
- * per step (beyond: EDM_HIP_ERR_ARG -- all-samples deposition of a large system keeps edm_hip_bias_pair_step).  edm_hip_bias_pair_step evaluates every force of the step on the bias as it stands after
+ * tile's records behind every hill that reached it (~3 MB for the ~125 hills of a 1 M-pair step), for at most 16 384
+ * hills per pass.  On one rank a step with more hills (all-samples deposition of a large system) runs its force pass in
+ * segments of that many hills (edm_hip_bias_set "ordered_segment_hills"), each starting from the records the one
+ * before it left -- same forces, no limit on the hills of a step; d_first_sample must then ascend (EDM_HIP_ERR_ARG
+ * otherwise), as the fix's pair order does.  With a communicator the limit remains (beyond: EDM_HIP_ERR_ARG): the
+ * reference's MPI build flushes its send buffer every 2 048 hills in the middle of the loop (edm_bias.cpp:459-461), a
+ * design of its own.  edm_hip_bias_pair_step evaluates every force of the step on the bias as it stands after
  * pre_add_hill instead: faster (the forces share the selection's launch), and on a hill step its forces differ from
  * the reference's by the bias the step itself deposits (INTEGRATION.md has the measured size). */
 int edm_hip_bias_pair_step_ordered(edm_hip_bias *b, long long n, const double *d_r, double *d_force,
@@ -380,7 +385,9 @@ edm_hip_grid *edm_hip_bias_histogram(edm_hip_bias *b);
  * state): dim, b_tempering, b_targeting, global_tempering, bias_factor, boltzmann_factor,
  * temperature, hill_prefactor, bias_per_step, hill_density, cum_bias, total_volume,
  * expected_target, b_outofbounds, overflow_left, overflow_right, b_skip_hill_add,
- * hills_added, steps, mpi_rank, mpi_size.  Unknown name -> EDM_HIP_ERR_ARG. */
+ * hills_added, steps, mpi_rank, mpi_size -- and, of the reference-order pair step, ordered_segment_hills (hills per
+ * segment of its force pass; 0: the default, 16 384) and ordered_segments (segments the last such step's force pass
+ * used: 1 = one pass, 0 = no hill).  Unknown name -> EDM_HIP_ERR_ARG. */
 int edm_hip_bias_get(const edm_hip_bias *b, const char *name, double *value);
 int edm_hip_bias_set(edm_hip_bias *b, const char *name, double value);
 /* bias_dx, bias_sigma, min, max (dim doubles) */
