@@ -379,6 +379,8 @@ struct edm_hip_bias {
   long long ord_segment_hills = 0;   // edm_hip_bias_set("ordered_segment_hills"): hills per segment (0: ordered_max_hills())
   long long ord_segments = 0;        // edm_hip_bias_get("ordered_segments"): segments of the last reference-order step's
                                      // force pass (1: one pass, 0: no hill)
+  long long ord_window_passes = 0;   // edm_hip_bias_get("ordered_window_passes"): force passes (a segment: one) that ran
+                                     // the LDS-window form, k_pair_forces_ordered_win
   DevBuf<double> ord_base;           // the records behind the segments so far: two grids, written and read in turn
   DevBuf<long long> ord_starts;      // first pair of every segment (launch_ordered_segment_starts)
   DevBuf<int> ord_ahead, ord_first2;   // OrderedForcesArgs::dirty_ahead per segment / first samples 2 k (none given)
@@ -1731,8 +1733,10 @@ static int ordered_segments_enqueue(edm_hip_bias *b) {
     a.first_sample = first + p0;
     a.force = oe.d_force + p0;
     int nb = 0;
-    EDM_HIP_TRY(launch_pair_forces_ordered(g->g, a, b->ord_seg_partials.p + nparts, s, &nb, 0));
+    bool win = false;
+    EDM_HIP_TRY(launch_pair_forces_ordered(g->g, a, b->ord_seg_partials.p + nparts, s, &nb, &win, 0));
     nparts += nb;
+    b->ord_window_passes += win;
   }
   // (the energy: untagged partial sums, which the host reads behind its wait for the stream)
   oe.tag = 0;
@@ -1772,7 +1776,9 @@ static int ordered_forces_enqueue(edm_hip_bias *b) {
   a.force = b->ord_early.d_force;
   hipEvent_t e0, e1;
   profile_slot(g, &e0, &e1);
-  EDM_HIP_TRY(launch_pair_forces_ordered(g->g, a, g->d_partials, s, &b->ord_early.nblk, b->ord_early.tag, e0, e1));
+  bool win = false;
+  EDM_HIP_TRY(launch_pair_forces_ordered(g->g, a, g->d_partials, s, &b->ord_early.nblk, &win, b->ord_early.tag, e0, e1));
+  b->ord_window_passes += win;
   return EDM_HIP_OK;
 }
 
@@ -2434,6 +2440,7 @@ int edm_hip_bias_get(const edm_hip_bias *b, const char *name, double *value) {
   G("host_add_threads", b->host_add_threads)
   G("ordered_segment_hills", b->ord_segment_hills)
   G("ordered_segments", b->ord_segments)
+  G("ordered_window_passes", b->ord_window_passes)
 #undef G
   set_error(std::string("unknown EDMBias member ") + name);
   return EDM_HIP_ERR_ARG;

@@ -195,9 +195,10 @@ size_t ordered_count_shorts(const Geom &g, long long nh_cap);
 long long ordered_max_hills();
 bool ordered_forces_supported(const Geom &g);
 hipError_t launch_ordered_records(const Geom &g, const Tables &t, const OrderedForcesArgs &a, hipStream_t s);
-// tagged partial energy sums like launch_pair_forces (tag != 0: scratch is host-mapped, polled by the host)
+// tagged partial energy sums like launch_pair_forces (tag != 0: scratch is host-mapped, polled by the host);
+// window_out (may be NULL) receives whether the LDS-window form (k_pair_forces_ordered_win) was launched
 hipError_t launch_pair_forces_ordered(const Geom &g, const OrderedForcesArgs &a, double *scratch, hipStream_t s,
-                                      int *blocks_out, unsigned long long tag, hipEvent_t ev0 = nullptr,
+                                      int *blocks_out, bool *window_out, unsigned long long tag, hipEvent_t ev0 = nullptr,
                                       hipEvent_t ev1 = nullptr);
 // the same pass over a device-resident neighbour list (a.n / r / first_sample / force unused: list entry e is
 // "pair" e, its first sample 2 e; pl.fdelta receives the per-atom sums, pl.partial_tag as in launch_pairlist_forces)

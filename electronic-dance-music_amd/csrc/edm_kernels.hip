@@ -5876,7 +5876,9 @@ __global__ void __launch_bounds__(FAST_BLOCK) k_pair_forces_ordered_win(Geom g, 
 }
 
 hipError_t launch_pair_forces_ordered(const Geom &g, const OrderedForcesArgs &a, double *scratch, hipStream_t s,
-                                      int *blocks_out, unsigned long long tag, hipEvent_t ev0, hipEvent_t ev1) {
+                                      int *blocks_out, bool *window_out, unsigned long long tag, hipEvent_t ev0,
+                                      hipEvent_t ev1) {
+  if (window_out) *window_out = false;
   if (!ordered_forces_supported(g) || a.nh_cap > ORD_MAX_HILLS) return hipErrorInvalidValue;
   // long arrays: the LDS-window form (see k_pair_forces_ordered_win), where a workgroup's run of pairs spans few hills
   static const bool win_env = !test_force("no_k1o_window");   // (tests: the short-array kernel on long arrays too)
@@ -5906,6 +5908,7 @@ hipError_t launch_pair_forces_ordered(const Geom &g, const OrderedForcesArgs &a,
     EDM_LAUNCH_TIMED(k_pair_forces_ordered_win, dim3((unsigned)blocks), dim3(FAST_BLOCK), lds, s, ev0, ev1, g, a, dpw, scratch, tag,
                      per_block, w0, wn);
     if (blocks_out) *blocks_out = blocks;
+    if (window_out) *window_out = true;
     return hipGetLastError();
   }
   // four pairs per thread: 17.8 us per 1 M pairs; two or one (more workgroups, each paying the prologue that stages the

@@ -387,7 +387,8 @@ edm_hip_grid *edm_hip_bias_histogram(edm_hip_bias *b);
  * expected_target, b_outofbounds, overflow_left, overflow_right, b_skip_hill_add,
  * hills_added, steps, mpi_rank, mpi_size -- and, of the reference-order pair step, ordered_segment_hills (hills per
  * segment of its force pass; 0: the default, 16 384) and ordered_segments (segments the last such step's force pass
- * used: 1 = one pass, 0 = no hill).  Unknown name -> EDM_HIP_ERR_ARG. */
+ * used: 1 = one pass, 0 = no hill) and ordered_window_passes (read only: the force passes of such steps on this object,
+ * a segment counting as one, that ran the LDS-window form k_pair_forces_ordered_win).  Unknown name -> EDM_HIP_ERR_ARG. */
 int edm_hip_bias_get(const edm_hip_bias *b, const char *name, double *value);
 int edm_hip_bias_set(edm_hip_bias *b, const char *name, double value);
 /* bias_dx, bias_sigma, min, max (dim doubles) */

@@ -137,6 +137,8 @@ class Lib:
         s("bias_get", C.c_double, [vp, C.c_char_p])
         s("bias_set", None, [vp, C.c_char_p, C.c_double])
         s("bias_array", c_dp, [vp, C.c_char_p])
+        if hasattr(self.dll, self.prefix + "bias_add_hill_list"):   # (the oracle only)
+            s("bias_add_hill_list", None, [vp, C.c_int, c_dp, c_dp])
         if hasattr(self.dll, self.prefix + "mpi_rank"):   # (the reference builds only)
             s("mpi_rank", C.c_int, [])
             s("mpi_size", C.c_int, [])
@@ -431,6 +433,13 @@ class Bias:
         e = self.lib.fn("bias_pair_loop")(self.h, len(r), _dp(r), sec.ctypes.data_as(c_ip), _dp(ru), int(hill_step),
                                           int(est), _dp(force), nc.ctypes.data_as(c_ip))
         return e, force, int(nc[0])
+
+    def add_hill_list(self, x, runiform):
+        """add_hill(x[i], runiform[i]) for every i in order, in one C call (1-D; between pre_add_hill and
+        post_add_hill)"""
+        x, ru = _vec(x), _vec(runiform)
+        assert len(ru) >= len(x)
+        self.lib.fn("bias_add_hill_list")(self.h, len(x), _dp(x), _dp(ru))
 
     def write_bias(self, filename):
         self.lib.fn("bias_write_bias")(self.h, os.fsencode(filename))

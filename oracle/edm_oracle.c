@@ -1314,6 +1314,13 @@ double ora_bias_pair_loop(ora_bias *b, int n, const double *r, const int *second
   return energy;
 }
 
+/* n add_hill calls in list order (position x[i], uniform u[i]) between a caller's pre_add_hill and post_add_hill: the
+ * hill half of the batched fix's step (keyword batch_order), whose forces all read the bias as pre_add_hill left it */
+void ora_bias_add_hill_list(ora_bias *b, int n, const double *x, const double *runiform) {
+  int i;
+  for (i = 0; i < n; i++) ora_bias_add_hill(b, &x[i], runiform[i]);
+}
+
 /* edm_bias.cpp:224-262: the serial build routes all three writers to the
  * plain PLUMED writer. */
 void ora_bias_write_bias(const ora_bias *b, const char *filename) { ora_gauss_write(b->bias, filename); }

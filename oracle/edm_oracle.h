@@ -114,6 +114,9 @@ void ora_bias_post_add_hill(ora_bias *b);
  * update_force, then one add_hill (two when second[k]); see edm_oracle.c */
 double ora_bias_pair_loop(ora_bias *b, int n, const double *r, const int *second, const double *runiform,
                           int hill_step, int est_hill_count, double *force, int *ncalls);
+/* n add_hill calls (1-D positions x[n], uniforms runiform[n]) in list order; the caller brackets them with
+ * pre_add_hill / post_add_hill (oracle only: no reference counterpart) */
+void ora_bias_add_hill_list(ora_bias *b, int n, const double *x, const double *runiform);
 void ora_bias_write_bias(const ora_bias *b, const char *filename);
 void ora_bias_write_lammps_table(const ora_bias *b, const char *filename);
 void ora_bias_write_histogram(const ora_bias *b);
